@@ -1,6 +1,7 @@
 """Throughput of the planar bundle-adjustment training step on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c1|c5] [--precision bf16x3|fp16x2|bf16|fp16|fp32]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -14,7 +15,15 @@ operands with fp32 accumulation: forward hi*hi+hi*lo+lo*hi, dgrad W_hi^T dz + W_
 §4).  --precision bf16 (plain bf16 MFMA) and fp32 are the other recipes.  Synthetic targets (smooth procedural RGB, seed 0), Bernoulli(0.85) masks (seed 1),
 warps ~ N(0, 0.01^2) (seed 2, patch 0 fixed).  Weak scaling: 64 patches per GPU at every N.
 
-Prints one JSON line (rank 0).  `value` = pixels processed by all ranks per second.
+Prints one JSON line (rank 0).  `value` = pixels processed by all ranks per second, `ms_per_step` =
+the wall time of the K timed steps / K.
+
+A plain run sets up, warms up, times the K steps and prints the line: nothing else touches the GPU.
+--dump-outputs DIR then writes what the last timed step returned to its caller (dump_outputs) as
+DIR/<name>.npy.  --full adds everything else the benchmark measures: HIP events around the dominant
+kernel inside the timed region and its roofline, and, in runs of their own after the timed steps,
+the per-kernel breakdown, the forward-only render rate, the prologue GB/s, the CPU baseline and the
+fp16x2 leg (--no-cpu-baseline, --no-render and --no-alt-recipe drop single legs of it).
 """
 import argparse
 import json
@@ -100,8 +109,24 @@ def make_opt(cfg, precision, B_total, c2f=True):
     if canvas:
         over.update(H=canvas, W=canvas, patch_H=crop, patch_W=crop)
     opt = options.override_options(opt, edict(over))
-    opt.output_path = os.path.join(ROOT, "output", "bench")
+    opt.output_path = _scratch_dir()
     return opt
+
+
+_SCRATCH = []
+
+
+def _scratch_dir():
+    """The Model's output directory (it creates one; a benchmark step writes nothing into it): a
+    temporary directory of this process, removed at exit, so the benchmark also runs from a
+    checkout it may not write to."""
+    if not _SCRATCH:
+        import atexit
+        import shutil
+        import tempfile
+        _SCRATCH.append(tempfile.mkdtemp(prefix="marf_bench_"))
+        atexit.register(shutil.rmtree, _SCRATCH[0], ignore_errors=True)
+    return _SCRATCH[0]
 
 
 def synthetic_inputs(B_total, h, w, device):
@@ -192,6 +217,39 @@ def prologue_rate(graph, var, L, c2f, n=20):
     nbytes = 16 * gt.shape[0] * gt.shape[2] * gt.shape[3]
     return {"kernel": "prologue_probe", "algorithmic_bytes_per_launch": nbytes, "avg_launch_ms": s * 1e3,
             "achieved": nbytes / s / 1e9, "unit": "GB/s", "peak": PEAK_HBM / 1e9, "frac": nbytes / s / PEAK_HBM}
+
+
+DUMP_BUDGET = 60 * 10 ** 6  # bytes --dump-outputs may write in all (under 64 MB with the .npy headers)
+
+
+def dump_outputs(out_dir, m, v, loss):
+    """--dump-outputs: what the last timed step handed back, as <out_dir>/<name>.npy (float32; this
+    rank's shard): the rgb loss, the gradients the step left on the MLP and on the warp parameters,
+    both after the optimizer step, and the predicted colours (rows of rgb_prediction).  All files
+    together stay within DUMP_BUDGET: where every row does not fit, a fixed seed-0 sample of the
+    rows is written, with their indices in rgb_prediction_rows (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    g = m.graph
+
+    def flat(ts):
+        return torch.cat([t.detach().reshape(-1).float() for t in ts]).cpu().numpy()
+
+    mlp = [p for l in g.neural_image.mlp for p in (l.weight, l.bias)]
+    arrays = {"loss_rgb": np.asarray([float(loss.rgb.detach())], np.float32),
+              "mlp_params": flat(mlp), "warp_params": flat([g.warp_param.weight])}
+    if all(p.grad is not None for p in mlp):
+        arrays["mlp_grads"] = flat([p.grad for p in mlp])
+    if g.warp_param.weight.grad is not None:
+        arrays["warp_grads"] = flat([g.warp_param.weight.grad])
+    rgb = v.rgb_prediction.detach().reshape(-1, 3)
+    left = DUMP_BUDGET - sum(a.nbytes for a in arrays.values())
+    if rgb.shape[0] * 12 > left:  # a sampled row costs 12 bytes of colour and 8 of index
+        rows = np.sort(np.random.default_rng(0).choice(rgb.shape[0], size=max(left, 0) // 20, replace=False))
+        rgb = rgb[torch.from_numpy(rows).to(rgb.device)]
+        arrays["rgb_prediction_rows"] = rows.astype(np.float64)
+    arrays["rgb_prediction"] = rgb.float().cpu().numpy()
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def _free_port():
@@ -305,6 +363,11 @@ def main():
                          "the per-kernel times and the roofline then come from eager steps")
     ap.add_argument("--no-alt-recipe", action="store_true",
                     help="skip the second leg (one GPU, c3, bf16x3 only): the same workload in the fp16x2 recipe")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: dominant-kernel events and roofline, per-kernel "
+                         "breakdown, render rate, prologue GB/s, CPU baseline, the fp16x2 leg")
     ap.add_argument("--launch-check", action="store_true",
                     help="set up the ranks and print the JSON line's world size / backend only (no GPU work)")
     args = ap.parse_args()
@@ -376,14 +439,16 @@ def main():
     if args.graph and not m.graph_capable():
         raise SystemExit("--graph: the step cannot be captured here (one process, use_edges off)")
 
+    last = {}  # the var bundle the latest step returned (--dump-outputs)
+
     def step(eager=False):
         if args.graph and not eager:
             # the whole iteration replayed: forward, loss, backward, Adam, progress, fix_first
-            v, loss = m.captured_step(var)
+            last["v"], loss = m.captured_step(var)
             graph.neural_image.progress.data.fill_(0.2)  # keep c2f partially on
             return loss
         m.optim.zero_grad()
-        v = graph.forward(var, mode="train")
+        last["v"] = v = graph.forward(var, mode="train")
         loss = m._loss_sum(graph.compute_loss(v, mode="train"))  # summarize_loss without host syncs
         loss.all.backward()
         m.all_reduce_grads()
@@ -401,19 +466,65 @@ def main():
     for _ in range(args.warmup):
         loss = step()
     barrier()
-    # timed region: HIP events around the dominant kernel only (the fused step's launches; every
+    # timed region; --full: HIP events around the dominant kernel only (the fused step's launches; every
     # event pair adds a few microseconds between launches, so the other kernels are timed after)
-    marf_hip.profile_reset()
-    marf_hip.profile_filter(["mlp_step"])
-    marf_hip.profile_enable(True)
-    barrier()
+    if args.full:
+        marf_hip.profile_reset()
+        marf_hip.profile_filter(["mlp_step"])
+        marf_hip.profile_enable(True)
+        barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         loss = step()
     barrier()
     elapsed = time.perf_counter() - t0
-    marf_hip.profile_enable(False)
-    prof = marf_hip.profile_read()
+    if args.full:
+        marf_hip.profile_enable(False)
+        prof = marf_hip.profile_read()
+    if args.dump_outputs and rank == 0:  # before anything else steps the model
+        dump_outputs(args.dump_outputs, m, last["v"], loss)
+    t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
+    if world > 1:
+        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
+    elapsed = float(t)
+    loss_v = float(loss.rgb.detach())
+    timing_only = os.environ.get("MARF_AB_TIMING_ONLY") == "1"  # A/B builds whose results are wrong on purpose
+    assert np.isfinite(loss_v) or timing_only, "loss is not finite"
+    step_kernel = graph.neural_image.engine(dev).net.step_kernel
+    dims = [2 + 4 * L] + hidden + [3]
+    peak = PEAK_FP32 if args.precision == "fp32" else PEAK_BF16
+    ms = elapsed / args.steps * 1e3
+    value = world * px_local / (elapsed / args.steps)
+    F = flops_per_px(dims)
+    out = {
+        "metric": METRIC, "value": value, "unit": "pixels/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": ms, "higher_is_better": True, "scaling": "strong" if args.strong else "weak",
+        "vs_baseline": None, "dtype": args.precision, "data": "synthetic (procedural targets, Bernoulli masks, random warps; reference-style init)",
+        "config": {"workload": f"{args.config}: {per_gpu} patches x {h}x{w} px per GPU, L={L}, MLP "
+                               f"{'-'.join(map(str, dims))}, {RECIPES[args.precision]}, "
+                               + ("c2f off" if args.no_c2f else "c2f [0,0.4] at progress 0.2"),
+                   "patches_per_gpu": per_gpu, "pixels_per_step_per_gpu": px_local,
+                   "pixels_per_s_per_gpu": value / world, "parallelism": f"dp{world} (patches)",
+                   "algorithmic_flops_per_px": F,
+                   "step_tflops_per_gpu": value / world * F / 1e12,
+                   "step_frac_of_peak": value / world * F / peak,
+                   "loss_rgb_last": loss_v,
+                   "step_kernel": step_kernel},
+        "dist": dist,
+        "graph": bool(args.graph),
+        "full": bool(args.full),
+    }
+    if timing_only:
+        out["timing_only"] = True  # never a headline: the build under test computes wrong results
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            torch.distributed.barrier()
+            torch.distributed.destroy_process_group()
+        return
+
+    # ---- --full: what the benchmark measures beside its headline, each leg after the timed steps
     # per-kernel breakdown: a separate pass of the same step with every kernel timed (eager: a
     # replayed graph records no events)
     n_break = max(3, args.steps // 4)
@@ -427,14 +538,6 @@ def main():
     prof_all = marf_hip.profile_read()
     if args.graph:  # the dominant kernel's duration from the eager steps
         prof = {k: (v[0] * args.steps / n_break, v[1] * args.steps // n_break) for k, v in prof_all.items()}
-    t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
-    if world > 1:
-        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
-    elapsed = float(t)
-    loss_v = float(loss.rgb.detach())
-    timing_only = os.environ.get("MARF_AB_TIMING_ONLY") == "1"  # A/B builds whose results are wrong on purpose
-    assert np.isfinite(loss_v) or timing_only, "loss is not finite"
-    step_kernel = graph.neural_image.engine(dev).net.step_kernel
 
     # ---- forward-only render rate (reported beside the step): Graph.forward without
     #      grad = grid -> warp -> posenc -> MLP -> rgb over the same patches (k_mlp_fwd, no saves)
@@ -461,7 +564,6 @@ def main():
     #      (mfma_*), not in `achieved`.  HBM: algorithmic 16 B/px (target + mask) + 12 B/px (rgb
     #      out); the saved layer inputs / pre-activation gradients the weight-gradient kernels read
     #      back are the design's own traffic (design_bytes_per_launch), not algorithmic.
-    dims = [2 + 4 * L] + hidden + [3]
     Kp0 = (dims[0] + 31) // 32 * 32
     S = (b1 - b0) * ((h * w + 127) // 128 * 128)
     sum_mac = sum(a * b for a, b in zip(dims[:-1], dims[1:]))
@@ -478,7 +580,6 @@ def main():
     # includes waiting for free CUs): reported, not summed
     step_kernel_ms = sum(v[0] for k, v in prof_all.items() if not k.endswith("_side")) / n_break
     dom = max(prof.items(), key=lambda kv: kv[1][0])[0] if prof else None
-    peak = PEAK_FP32 if args.precision == "fp32" else PEAK_BF16
     roof = None
     if dom in kflops:
         # per step: a pipelined step (marf_net_set_pipeline) runs the step kernel in several
@@ -504,27 +605,10 @@ def main():
                 "valu_per_mfma": tr[2].get("valu_per_mfma") if tr else None,
                 "vmem_rd_insts_per_launch": tr[2].get("SQ_INSTS_VMEM_RD") if tr else None}
     prologue = prologue_rate(graph, var, L, opt.barf_c2f) if world == 1 or rank == 0 else None
-    ms = elapsed / args.steps * 1e3
-    value = world * px_local / (elapsed / args.steps)
-    F = flops_per_px(dims)
-    out = {
-        "metric": METRIC, "value": value, "unit": "pixels/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": ms, "higher_is_better": True, "scaling": "strong" if args.strong else "weak",
-        "vs_baseline": None, "dtype": args.precision, "data": "synthetic (procedural targets, Bernoulli masks, random warps; reference-style init)",
-        "config": {"workload": f"{args.config}: {per_gpu} patches x {h}x{w} px per GPU, L={L}, MLP "
-                               f"{'-'.join(map(str, dims))}, {RECIPES[args.precision]}, "
-                               + ("c2f off" if args.no_c2f else "c2f [0,0.4] at progress 0.2"),
-                   "patches_per_gpu": per_gpu, "pixels_per_step_per_gpu": px_local,
-                   "pixels_per_s_per_gpu": value / world, "parallelism": f"dp{world} (patches)",
-                   "algorithmic_flops_per_px": F,
-                   "step_tflops_per_gpu": value / world * F / 1e12,
-                   "step_frac_of_peak": value / world * F / peak,
-                   "loss_rgb_last": loss_v,
-                   "step_kernel": step_kernel,
-                   "render_pixels_per_s": render_pps},
+    out["config"]["render_pixels_per_s"] = render_pps
+    out.update({
         "roofline": roof,
         "prologue": prologue,
-        "dist": dist,
         "kernels": per_kernel,
         "kernel_ms_per_step": step_kernel_ms,
         "kernels_note": f"per-kernel HIP-event durations from {n_break} further eager steps with every kernel "
@@ -532,14 +616,12 @@ def main():
                         "the timed region times the dominant kernel only"
                         + ("; with --graph it replays a captured graph and the roofline uses these eager steps)"
                            if args.graph else ")"),
-        "graph": bool(args.graph),
-    }
-    if timing_only:
-        out["timing_only"] = True  # never a headline: the build under test computes wrong results
+    })
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.config, args.cpu_sample_patches)
     if (world == 1 and args.config == "c3" and args.precision == "bf16x3" and not args.no_alt_recipe
             and not args.strong and not args.no_c2f and not args.graph and not timing_only):
+        last.clear()
         del m, graph, var, loss
         torch.cuda.empty_cache()
         out["alt_recipe"] = alt_recipe(args, dev)

@@ -89,7 +89,9 @@ def make_prologue():
                 enc = ni.positional_encoding(uv[:, idx[:256]])
                 key = f"{tag}_enc_L{L}_{'c2f' if c2f else 'full'}_p{p}"
                 out[key] = np32(enc)
-    np.savez_compressed(os.path.join(HERE, "prologue.npz"), **out)
+    for tag in ("c1", "c3"):  # one file per geometry: each stays under the 1 MiB limit for a committed file
+        np.savez_compressed(os.path.join(HERE, f"prologue_{tag}.npz"),
+                            **{k: v for k, v in out.items() if k.startswith(tag + "_")})
 
 
 # ---------------------------------------------------------------- training step

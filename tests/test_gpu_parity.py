@@ -83,7 +83,7 @@ def test_lie_exp_backward_bitexact():
 @pytest.mark.parametrize("tag", ["c1", "c3"])
 def test_grid_and_warp_bitexact(tag):
     from warp import Warp
-    z = g("prologue")
+    z = g(f"prologue_{tag}")
     H, W, ph, pw, B = (int(x) for x in z[f"{tag}_geo"])
     opt = make_opt(H=H, W=W, patch_H=ph, patch_W=pw, batch_size=B)
     wp = Warp(opt)
@@ -101,7 +101,7 @@ def test_grid_and_warp_bitexact(tag):
 @pytest.mark.parametrize("tag", ["c1", "c3"])
 def test_posenc_c2f(tag):
     from model.planar import NeuralImageFunction
-    z = g("prologue")
+    z = g(f"prologue_{tag}")
     uv = t(z[f"{tag}_uv"][:, :256])
     n = 0
     for key in z.files:

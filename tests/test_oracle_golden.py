@@ -27,7 +27,7 @@ def test_lie_exp_backward_bitexact(golden):
 
 @pytest.mark.parametrize("tag", ["c1", "c3"])
 def test_grid_and_warp_bitexact(golden, tag):
-    g = golden("prologue")
+    g = golden(f"prologue_{tag}")
     H, W, ph, pw, B = (int(x) for x in g[f"{tag}_geo"])
     xy = oracle.pixel_grid(H, W, ph, pw, crop=True)
     assert np.array_equal(xy[g[f"{tag}_idx"]], g[f"{tag}_xy"])
@@ -41,7 +41,7 @@ def test_grid_and_warp_bitexact(golden, tag):
 
 @pytest.mark.parametrize("tag", ["c1", "c3"])
 def test_posenc_c2f(golden, tag):
-    g = golden("prologue")
+    g = golden(f"prologue_{tag}")
     uv = g[f"{tag}_uv"][:, :256]
     n = 0
     for key in g.files:

@@ -18,7 +18,7 @@ done
 for rep in 1 2; do
   for v in old new; do
     if [ $v = old ]; then L=$LIBD/libmarf_old.so; else L=""; fi
-    MARF_LIB=$L timeout -k 10 200 python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-render > $OUT/bench_$v.json 2> $OUT/bench_$v.err || { echo "bench $v failed"; tail -5 $OUT/bench_$v.err; exit 1; }
+    MARF_LIB=$L timeout -k 10 200 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-render > $OUT/bench_$v.json 2> $OUT/bench_$v.err || { echo "bench $v failed"; tail -5 $OUT/bench_$v.err; exit 1; }
     python - $OUT/bench_$v.json $v <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -12,7 +12,7 @@ while read -r CTRS; do
   [ -z "$CTRS" ] && continue
   i=$((i+1))
   timeout -s KILL 120 rocprofv3 --pmc $CTRS --kernel-trace --output-format csv -d $OUT/pass$i -o run \
-     --kernel-include-regex "k_step2" -- python3 $ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-render > $OUT/pass$i.log 2>&1
+     --kernel-include-regex "k_step2" -- python3 $ROOT/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-render > $OUT/pass$i.log 2>&1
   rc=$?
   echo "pass $i ($CTRS): exit $rc"
   [ $rc -ne 0 ] && { tail -5 $OUT/pass$i.log; break; }
