@@ -872,6 +872,8 @@ struct Step2BufPlan {
     size_t feat[MARF_MAX_LAYERS], dz[MARF_MAX_LAYERS];
     size_t dH, loss, blast, wlast, dummy, c2f, kmap, part, bpart, total;
     size_t partl[MARF_MAX_LAYERS], bpartl[MARF_MAX_LAYERS];  // per-layer split-K partials (pipelined / fused)
+    bool dzl;                      // dz_{n-1} is recomputed by layer n-2's weight gradient (dzl_recompute):
+    size_t dzl_g, dzl_mk, dzl_w;   // not allocated; these (marf_args.h DZL_G_SET ..) take its place
     int grid, n_tiles;
     int nblk;  // per-block partial sets of the step kernel (all pieces' blocks)
     long long S;
@@ -924,6 +926,25 @@ static bool l0_recompute(const marf_net* n, const GeoDev& g, long long S) {
     const long long chunk = wgrad_chunk(S);
     return marf_wgrad_l0_recompute_ok(n->Mp[0], n->Kp[1], n->s2.ldf0, S, (int)chunk, (int)((S + chunk - 1) / chunk),
                                       g.Np_pad);
+}
+
+// The weight gradient of the last hidden layer (n-2) recomputes dz_{n-1} = relu'(z) (W_{n-1}^T g), a
+// rank-3 function of the pixel, from the 48 B / pixel the step kernel stores in its place (the g
+// fragment and the ReLU mask words, marf_args.h), so the step kernel does not store its 512 B /
+// pixel (MARF_DZL_RECOMPUTE=0: store and read, for A/B).  The bf16 split recipe (k_step2's
+// instantiations and its generic kernel; not k_step2dz, not fp16x2) with every hidden layer 256
+// wide, on the LDS-DMA weight-gradient kernel, fused or per-layer launches, pipeline off.  Decided
+// in plan_step2_bufs, which the forward and the backward both go through.
+static bool dzl_recompute(const marf_net* n, const GeoDev& g, long long S, bool pipe_on) {
+    const char* e = getenv("MARF_DZL_RECOMPUTE");
+    if (e && e[0] == '0') return false;
+    const int nl = n->n_layers;
+    if (n->s2.variant != 1 || n->s2.dz || pipe_on || g.mode != MARF_GEO_GRID || nl < 3 || n->s2.NMW != 4) return false;
+    for (int l = 0; l < nl - 1; ++l)
+        if (n->Mp[l] != 256 || (l > 0 && n->Kp[l] != 256)) return false;
+    const long long chunk = wgrad_chunk(S);
+    return marf_wgrad_dzl_ok(n->Mp[nl - 2], n->Kp[nl - 1], n->Kp[nl - 2], n->Kp[nl - 2], S, (int)chunk,
+                             (int)((S + chunk - 1) / chunk));
 }
 
 // ---- pipelined weight gradients (large steps of the pixel-per-wave kernel)
@@ -1031,9 +1052,20 @@ static void plan_step2_bufs(const marf_net* n, const GeoDev& g, Step2BufPlan& p,
     // dz_l and the dH partials carry 32 NW sink rows past S: the dgrad pass of a pixel set that has
     // no tile (an odd tile count with two sets per dgrad pass) stores there
     const long long Ssink = p.S + q.TPX;
+    p.dzl = !render && dzl_recompute(n, g, p.S, p.pipe.on != 0);
     for (int l = 1; l < nl; ++l) {
         p.dz[l] = off;
+        if (p.dzl && l == nl - 1) continue;  // (recomputed: never stored)
         off += rup(Ssave * Ssink * n->Kp[l] * 2, 256);
+    }
+    p.dzl_g = p.dzl_mk = p.dzl_w = 0;
+    if (p.dzl) {  // per 32-pixel set, the sink sets included
+        p.dzl_g = off;
+        off += rup(Ssink / 32 * DZL_G_SET, 256);
+        p.dzl_mk = off;
+        off += rup(Ssink / 32 * DZL_MK_SET, 256);
+        p.dzl_w = off;
+        off += DZL_W_BYTES;
     }
     p.dH = off;
     off += rup(Ssave * Ssink / q.PX * 9 * 4, 256);
@@ -1165,6 +1197,11 @@ static int step2_forward(const marf_net* net, const marf_geometry* geo, const ma
     a.bias = (const float*)(pk + q.bias_off);
     a.nbias = q.nbias;
     a.feat0_recompute = !render && l0_recompute(net, a.geo, p.S) ? 1 : 0;
+    if (p.dzl) {
+        a.dzl_g = sv + p.dzl_g;
+        a.dzl_mk = sv + p.dzl_mk;
+        a.dzl_w = sv + p.dzl_w;
+    }
     a.gt = d_gt;
     a.mask = d_mask;
     a.rgb = d_rgb;
@@ -1176,7 +1213,7 @@ static int step2_forward(const marf_net* net, const marf_geometry* geo, const ma
         y.ldf = l == 0 ? q.ldf0 : net->Kp[l];
         y.ldz = net->Kp[l];
         y.feat = l < nl - 1 && !render ? (u16*)(sv + p.feat[l]) : nullptr;
-        y.dz = l >= 1 && !render ? (u16*)(sv + p.dz[l]) : nullptr;
+        y.dz = l >= 1 && !render && !(p.dzl && l == nl - 1) ? (u16*)(sv + p.dz[l]) : nullptr;
     }
     a.dH_partial = (float*)(sv + p.dH);
     a.loss_partial = (double*)(sv + p.loss);
@@ -1275,6 +1312,9 @@ static int step2_backward(const marf_net* net, const marf_geometry* geo, const v
     // the saved tensors' precision (fp16x2: fp16, carrying the dgrad's 2^10 gradient scale)
     const int sdt = q.variant == 3 ? 2 : 1;
     const float post = q.variant == 3 ? 1.0f / 1024.0f : 1.0f;
+    // layer n-2 rebuilds its dz_{n-1} from these (p.dzl: the step kernel stored them instead)
+    WgDzlSrc dzl_src = {nullptr, nullptr, nullptr};
+    if (p.dzl) dzl_src = {sv + p.dzl_g, sv + p.dzl_mk, sv + p.dzl_w};
     // The fused weight gradients (marf_launch_wgrad_fused): the hidden layers in one launch, layer 0
     // beside it on the side stream, every reduction in one launch -- the same partials and sums as
     // the per-layer launches below (bit-identical).  The layer events follow it, in the per-layer order.
@@ -1316,6 +1356,7 @@ static int step2_backward(const marf_net* net, const marf_geometry* geo, const v
             x.dW = d_dparams + net->w_off[l];
             x.db = d_dparams + net->b_off[l];
             x.kmap = l == 0 ? kmap : nullptr;
+            if (p.dzl && l == nl - 2) x.dzl = dzl_src;
         }
         if (marf_wgrad_fused_ok(Lf, nf, p.S, (int)chunk, n_chunks, g.Np_pad)) {
             PipeStreams* st = nullptr;
@@ -1399,7 +1440,8 @@ static int step2_backward(const marf_net* net, const marf_geometry* geo, const v
                            "step_backward wgrad_l0 (feat_0 recomputed)");
                 else
                     HIPCHK(marf_launch_wgrad(sdt, sv + p.dz[l + 1], net->Kp[l + 1], sv + p.feat[l], K, p.S, net->Mp[l], K,
-                                             (int)chunk, n_chunks, part, bpart, s, nullptr, true),
+                                             (int)chunk, n_chunks, part, bpart, s, nullptr, true,
+                                             p.dzl && l == nl - 2 ? &dzl_src : nullptr),
                            "step_backward wgrad");
             }
             {

@@ -71,6 +71,17 @@ struct PackArgs {
     PackLayer ly[MARF_MAX_LAYERS];
 };
 
+// ---- dz_{n-1} recomputed by the weight gradient of layer n-2.  Instead of the
+// 512 B / pixel of dz_{n-1} the step kernel stores what determines it, per 32-pixel set (= one
+// wave's pixels = 32 consecutive pixel slots):
+//   g    [S / 32 + NW][32][16 B]   the last-layer dgrad's B fragment of lane half 0 (pixel p:
+//                                  [g hi (3), 0, g lo (3), 0] bf16; lane half 1 holds zeros)
+//   mk   [S / 32 + NW][64][4]      the ReLU mask words of layer n-2's output: lane-major, word j =
+//                                  row tiles 2 j, 2 j + 1
+// and block 0 copies the 8 row tiles of the last-layer dgrad stage of the weight program, hi then lo
+// (1 KB each), into w.  (The NW sets past S: the sink of a dgrad pass's set without a tile.)
+constexpr int DZL_G_SET = 512, DZL_MK_SET = 1024, DZL_W_BYTES = 16384;
+
 // Per-layer constants, copied into LDS at kernel start (kept out of the SGPR file).
 struct S2Layer {
     int nrt;     // row tiles of the forward output (Mp / 32; last layer: 1)
@@ -110,6 +121,11 @@ struct Step2Args {
     int fwd_only;                    // render: forward stages only, rgb out, nothing saved
     int feat0_recompute;             // feat_0 is recomputed by the layer-0 weight gradient: not stored
     const float* pro_fallback;       // valid device address for the input DMA when gt / H are absent
+    // dz_{n-1} is recomputed by the weight gradient of layer n-2 (all null: stored as every dz_l): the
+    // per-set g fragments, mask words and the dgrad stage's weights it needs (DZL_G_SET .. above)
+    char* dzl_g;
+    char* dzl_mk;
+    char* dzl_w;
     // LDS layout (byte offsets; computed on the host)
     int lds_pro, lds_bias, lds_c2f, lds_layers, lds_wave, lds_wave_bytes, lds_total;
 };
@@ -149,6 +165,15 @@ struct WgRange {
     int n, part0;
 };
 bool marf_wgrad_range_ok(int dtype, int M, int ldz, int K, int ldf);
+// dz_{n-1} recomputed by the weight gradient of layer n-2 instead of read: what the step kernel
+// stored in its place (DZL_G_SET .. above: per-set g fragments and mask words, the dgrad stage's weights)
+struct WgDzlSrc {
+    const char* g;
+    const char* mk;
+    const char* w;
+};
+// the shape the recomputing instantiation takes: a 256 x 256 bf16 T16 layer on the LDS-DMA kernel
+bool marf_wgrad_dzl_ok(int M, int ldz, int K, int ldf, long long S, int chunk, int n_chunks);
 bool marf_wgrad_l0_recompute_ok(int M, int ldz, int ldf0, long long S, int chunk, int n_chunks, long long Np_pad);
 hipError_t marf_launch_wgrad_l0_recompute(const void* dz, int ldz, const GeoDev& geo, const float* c2f_w, int L,
                                           int nk0, int K0, long long S, int M, int chunk, int n_chunks, float* partial,
@@ -156,7 +181,7 @@ hipError_t marf_launch_wgrad_l0_recompute(const void* dz, int ldz, const GeoDev&
 // t16: dz / feat in the split-recipe step kernel's T16 block layout (marf_wgrad.hip t16_off)
 hipError_t marf_launch_wgrad(int dtype, const void* dz, int ldz, const void* feat, int ldf, long long S, int M, int K,
                              int chunk, int n_chunks, float* partial, float* bpartial, hipStream_t s,
-                             const WgRange* rng = nullptr, bool t16 = false);
+                             const WgRange* rng = nullptr, bool t16 = false, const WgDzlSrc* dzl = nullptr);
 // One layer of the fused weight-gradient launch (marf_launch_wgrad_fused): its split-K partials
 // [n_parts][M][K] (+ [n_parts][M] bias) and the fixed-order reduction into dW [Mo][Ko] / db [Mo].
 struct WgFusedLayer {
@@ -172,6 +197,7 @@ struct WgFusedLayer {
     float* dW;
     float* db;
     const int* kmap;          // layer 0: column of true input feature k in the partial
+    WgDzlSrc dzl;             // kind 0, g != null: dz is recomputed, not read (layer n-2)
 };
 // every kind-0 layer's chunk products in one launch on s, the layer-0 one (kind 1 or 2) beside it on
 // s2 (fork / join events), then every layer's reduction in one launch on s; false if a shape does

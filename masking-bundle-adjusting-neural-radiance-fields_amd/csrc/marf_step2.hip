@@ -30,19 +30,12 @@
 #include <type_traits>
 
 #include "marf_args.h"
+#include "marf_step2_dev.h"
 
 namespace marf {
 
 // ------------------------------------------------------------------ inline-asm memory ops
 
-// LDS-DMA, 4 B per lane (256 B per wave instruction)
-MARF_DEV void s2_glds4(const void* src, unsigned lds) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(src), "s"(lds)
-                 : "memory");
-}
 // Stores outside the compiler's bookkeeping: the s_nop covers the store-data hazard (the data
 // registers may be rewritten right after), which hipcc pads only for its own stores.
 typedef uint32_t s2_u32x2 __attribute__((ext_vector_type(2)));
@@ -75,39 +68,6 @@ MARF_DEV void s2_wait_vm() {
 
 MARF_DEV i16x4 s2_tr16(const u16* p) {
     return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) i16x4*)(p));
-}
-
-// compile-time loop: f(std::integral_constant<int, I>) for I = 0 .. N-1
-template <int... I, class F>
-MARF_DEV void s2_sfor_impl(std::integer_sequence<int, I...>, F&& f) {
-    (f(std::integral_constant<int, I>()), ...);
-}
-template <int N, class F>
-MARF_DEV void s2_sfor(F&& f) {
-    s2_sfor_impl(std::make_integer_sequence<int, N>(), f);
-}
-
-// two floats -> packed bf16 pair (v_cvt_pk_bf16_f32, RNE)
-MARF_DEV uint32_t s2_pk(float a, float b) {
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(((f32x2){a, b}), bf16x2));
-}
-MARF_DEV float s2_lo16(uint32_t w) { return __uint_as_float(w << 16); }
-MARF_DEV float s2_hi16(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
-
-union S2Frag {
-    bf16x8 f;
-    f16x8 h;  // (the fp16-forward recipe's operands)
-    uint4 u;
-    uint32_t w[4];
-};
-
-// two floats -> packed fp16 pair (v_cvt_pk_f16_f32, RNE)
-MARF_DEV uint32_t s2_pkh(float a, float b) {
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(((f32x2){a, b}), f16x2));
 }
 
 // 8 floats -> bf16 hi fragment (+ lo remainder fragment)
@@ -196,6 +156,9 @@ __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Ar
     // HF: the dgrad's gradient scale (the saved dz carry it; the host's weight-gradient reduction
     // multiplies by its inverse, marf_abi.hip step2_backward)
     constexpr float kGS = 1024.f;
+    // dz_{n-1} may be left to the weight gradient (Step2Args::dzl_g): the bf16 split recipe with a
+    // bf16 dz; k_step2dz and k_step2h keep the saved path (the host never sets dzl_g for them)
+    constexpr bool DZL_OK = SPLIT && !DZ && !HF && C::NMW == 4;
     constexpr int R0Q = NKH / (FIX ? NK0F : NKH);  // layer-0 row tiles per stage (the host's r0)
     constexpr int R0F = R0Q < 1 ? 1 : (R0Q > NRT ? NRT : R0Q);
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -234,6 +197,18 @@ __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Ar
         reinterpret_cast<uint32_t*>(lyr)[e] = reinterpret_cast<const uint32_t*>(a.layers)[e];
     for (int e = lane; e < 512; e += 64) reinterpret_cast<uint32_t*>(gts)[e] = 0u;
     for (int e = lane; e < 3 * a.Kl; e += 64) wla[e] = 0.f;
+    if constexpr (DZL_OK) {
+        // the last-layer dgrad stage's row tiles (hi, then lo) for the weight gradient that recomputes
+        // dz_{n-1}: the backward has no packed buffer at hand
+        if (a.dzl_w && blockIdx.x == 0) {
+            const uint4* src = reinterpret_cast<const uint4*>(a.prog + (size_t)a.n_fwd * C::SLOT);
+            uint4* dst = reinterpret_cast<uint4*>(a.dzl_w);
+            for (int e = threadIdx.x; e < 2 * NRT * 64; e += NW * 64) {
+                const int part = e / (NRT * 64);
+                dst[e] = src[part * (C::LO / 16) + (e - part * NRT * 64)];
+            }
+        }
+    }
 
     const int tpp = a.geo.Np_pad / C::TPX;   // block tiles per patch
     const int Np = a.geo.Np;
@@ -430,14 +405,9 @@ __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Ar
     //  2 rt, 2 rt + 1)
     auto store_rt = [&](u16* row0, auto rtc, const S2Frag& f0, const S2Frag& f1) {
         constexpr int rt = decltype(rtc)::value;
-        auto contig = [&](const S2Frag& f) -> uint4 {
-            const auto xz = __builtin_amdgcn_permlane32_swap(f.u.x, f.u.z, false, false);
-            const auto yw = __builtin_amdgcn_permlane32_swap(f.u.y, f.u.w, false, false);
-            return make_uint4(xz[0], yw[0], xz[1], yw[1]);
-        };
         u16* blk = row0 + 1024 * rt;  // (2 KB per row tile: past the 12-bit instruction offset)
-        s2_st16o<0>(blk, contig(f0));
-        s2_st16o<1024>(blk, contig(f1));
+        s2_st16o<0>(blk, s2_t16_contig(f0));
+        s2_st16o<1024>(blk, s2_t16_contig(f1));
         st_cur += 2;
     };
 
@@ -465,12 +435,8 @@ __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Ar
     typedef std::integral_constant<bool, false> PcOff;
     // one accumulation chain (a second, alternating accumulator measured no faster, and any change
     // of the summation order re-rolls the seed-3 basin: DESIGN.md §4)
-    auto mf = [&](f32x16& acc, const uint4& x, const S2Frag& y) {
-        if constexpr (HF)  // (the fp16x2 recipe: every MFMA in fp16)
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, x), y.h, acc, 0, 0, 0);
-        else
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, x), y.f, acc, 0, 0, 0);
-    };
+    // (the fp16x2 recipe: every MFMA in fp16)
+    auto mf = [&](f32x16& acc, const uint4& x, const S2Frag& y) { s2_mfma<HF>(acc, x, y); };
     // one 32-row output tile: acc (+)= A[ks] . B[ks] over NK k-steps from the slot
     //   MODE 0: plain; 1: split forward (hi.hi + hi.lo + lo.hi); 2: split dgrad (hi.B + lo.B)
     // With one wave per SIMD the issue is in order, so the filler work of a k-step goes INTO the
@@ -736,14 +702,14 @@ __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Ar
         constexpr int rt = decltype(rtc)::value;
         s2_sfor<8>([&](auto qc) {
             constexpr int q = decltype(qc)::value;
-            constexpr int b0 = 16 * 0 + 8 * (1 - (rt & 1)) + 7 - q, b1 = 16 * 1 + 8 * (1 - (rt & 1)) + 7 - q;
-            const float x0 = __int_as_float(__builtin_amdgcn_sbfe((int)es.mw, b0, 1) & __float_as_int(pa[2 * q]));
-            const float x1 = __int_as_float(__builtin_amdgcn_sbfe((int)es.mw, b1, 1) & __float_as_int(pa[2 * q + 1]));
+            float x0, x1;
+            s2_bmask_pair<rt & 1, q>(es.mw, pa, x0, x1);
             es.hw[q] = HF ? s2_pkh(x0, x1) : s2_pk(x0, x1);
             if constexpr (SDZ) es.lw[q] = s2_pk(x0 - s2_lo16(es.hw[q]), x1 - s2_hi16(es.hw[q]));
         });
     };
-    auto bfinish = [&](EpSt& es, S2Frag* O, auto rtc, u16* row0) {
+    // (save = false: the tile is not stored -- dz_{n-1} when the weight gradient recomputes it)
+    auto bfinish = [&](EpSt& es, S2Frag* O, auto rtc, u16* row0, bool save = true) {
         constexpr int rt = decltype(rtc)::value;
         O[2 * rt].u = make_uint4(es.hw[0], es.hw[1], es.hw[2], es.hw[3]);
         O[2 * rt + 1].u = make_uint4(es.hw[4], es.hw[5], es.hw[6], es.hw[7]);
@@ -751,7 +717,7 @@ __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Ar
             Ol[2 * rt].u = make_uint4(es.lw[0], es.lw[1], es.lw[2], es.lw[3]);
             Ol[2 * rt + 1].u = make_uint4(es.lw[4], es.lw[5], es.lw[6], es.lw[7]);
         }
-        store_rt(row0, rtc, O[2 * rt], O[2 * rt + 1]);
+        if (save) store_rt(row0, rtc, O[2 * rt], O[2 * rt + 1]);
     };
     // ---- the fp16x2 forward (HF): helpers
     // one 32-row output tile of BOTH pixel sets: c_s += A_hi . B_s + A_lo . B_s over NK k-steps (fp16
@@ -1543,6 +1509,23 @@ __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Ar
                     st_cur += 4;
                 }
             }
+            // dz_{n-1} recomputed by the weight gradient of layer n-2: instead of its row tiles, each
+            // set's g fragment (lane half 0) and its lanes' mask words of this layer -- two 16-B lane
+            // stores per set (marf_args.h DZL_G_SET ..)
+            bool save_dz = true;
+            if constexpr (DZL_OK) {
+                if (a.dzl_g) {
+                    save_dz = false;
+                    s2_sfor<NS>([&](auto sc) {
+                        constexpr int s = decltype(sc)::value;
+                        const size_t set = (size_t)(sl0[s] >> 5);
+                        const uint32_t* mk = mks_b(s) + lmask * C::NMW * 64 + lane;
+                        s2_st16(a.dzl_mk + set * DZL_MK_SET + lane * 16, make_uint4(mk[0], mk[64], mk[128], mk[192]));
+                        if (h == 0) s2_st16(a.dzl_g + set * DZL_G_SET + pxl * 16, gB[s].u);
+                        st_cur += 2;
+                    });
+                }
+            }
             s2_sfor<NRT>([&](auto rtc) {
                 constexpr int rt = decltype(rtc)::value;
                 if (rt < nrt) {
@@ -1568,14 +1551,14 @@ __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Ar
                                 }, PcOff());
                             }
                             S2T_BEGIN(11);
-                            bfinish(eb, Do[sp], std::integral_constant<int, rp>(), brow[sp]);
+                            bfinish(eb, Do[sp], std::integral_constant<int, rp>(), brow[sp], save_dz);
                             S2T_END(11);
                         }
                         if (s == NS - 1 && rt == nrt - 1) {
                             eb.mw = mks_b(s)[(lmask * C::NMW + (rt >> 1)) * 64 + lane];
                             if constexpr (FIX) bsteps_free(eb, cur, rtc);
                             else s2_sfor<16>([&](auto ec) { bstep(eb, cur, ec, rtc); });
-                            bfinish(eb, Do[s], rtc, brow[s]);
+                            bfinish(eb, Do[s], rtc, brow[s], save_dz);
                         }
                     });
                 } else {

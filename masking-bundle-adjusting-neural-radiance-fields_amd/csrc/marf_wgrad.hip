@@ -14,6 +14,7 @@
 //
 // 512 threads = 8 waves as 4 (rows) x 2 (cols); each wave owns RT x CT accumulator tiles.
 #include "marf_args.h"
+#include "marf_step2_dev.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -49,6 +50,7 @@ struct WgArgs {
     long long s_lo, s_len;
     int rng_n, part0;
     int t16;           // dz / feat in the step kernel's T16 block layout (t16_off), not row-major
+    WgDzlSrc dzl;      // g != null (k_wgrad_dma's DZL instantiations): dz is not read but recomputed
 };
 
 template <int RT, int CT>
@@ -282,9 +284,21 @@ MARF_DEV int foff(int r, int c) {
 
 // chunk `chunk_id` into output block `ob` (the body of one k_wgrad_dma block; also a work item of
 // k_wgrad_fused)
-template <class P, int NBUF, int SP, int KF, bool F0 = false, bool T16 = false>
+// DZL (the hidden layer n-2 of a split-recipe step, T16, 256 wide, 32-row stages; a.dzl.g != null):
+// the dz half of a ring slot is not filled by LDS-DMA -- dz_{n-1} = relu'(z) (W_{n-1}^T g) is rebuilt
+// from what the step kernel stored in its place (marf_args.h DZL_G_SET ..), with the step kernel's device
+// functions in its order (W_hi^T g, then W_lo^T g from a zero accumulator; mask; v_cvt_pk_bf16_f32;
+// the T16 permute), so the same bf16 bits land where the DMA would have put them.  A stage is one
+// 32-pixel set of the step kernel; wave w builds row tile w (feature blocks 2 w, 2 w + 1) from its
+// two weight fragments, loaded once per block.  The set's 1.5 KB of inputs travel through a ring of
+// their own (one 4-B LDS-DMA instruction per wave and stage, issued with the feat pieces of the stage
+// before, so the ring's in-order waits cover them), and the tile of stage st + 1 is built in
+// iteration st: one stage ahead of its use, never behind the barrier of the stage that consumes it.
+template <class P, int NBUF, int SP, int KF, bool F0 = false, bool T16 = false, bool DZL = false>
 MARF_DEV void wgrad_dma_body(const WgArgs& a, int chunk_id, int ob, char* smem) {
     static_assert(KF == 256 || KF == 96, "feat width");
+    static_assert(!DZL || (T16 && !F0 && KF == 256 && SP == 32 && std::is_same<P, PrecBF16>::value),
+                  "dz recompute: the bf16 T16 hidden layer, one 32-pixel set per stage");
     static_assert(!F0 || (KF == 96 && SP % 32 == 0), "feat_0 recompute: the 96-wide layer-0 stage, 32-row blocks");
     constexpr int WR = KF == 256 ? 4 : 8, WC = 8 / WR;  // wave grid over the 256 x KF output
     constexpr int RT = 256 / 32 / WR, CT = KF / 32 / WC;
@@ -318,6 +332,20 @@ MARF_DEV void wgrad_dma_body(const WgArgs& a, int chunk_id, int ob, char* smem) 
 
     const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
     const unsigned junk = lds0 + NBUF * STB;     // 1 KB sink for the idle feat rounds
+    // DZL: the sets' inputs, NBUF + 1 slots of [mask words 1 KB][g 512 B] behind the ring, then a
+    // 256-B sink; the wave's row tile of W_{n-1}^T (hi, lo), drained before the ring starts
+    constexpr int DZL_SLOT = DZL_MK_SET + DZL_G_SET, DZL_SM0 = NBUF * STB;
+    const bool dzl = DZL && a.dzl.g != nullptr;  // (block-uniform)
+    uint4 dzl_whi = make_uint4(0, 0, 0, 0), dzl_wlo = make_uint4(0, 0, 0, 0);
+    if constexpr (DZL) {
+        if (dzl) {
+            dzl_whi = *reinterpret_cast<const uint4*>(a.dzl.w + wave * 1024 + lane * 16);
+            dzl_wlo = *reinterpret_cast<const uint4*>(a.dzl.w + DZL_W_BYTES / 2 + wave * 1024 + lane * 16);
+            // (the compiler's wait for the loads: here, not at their first use inside the ring)
+            asm volatile("" ::"v"(dzl_whi.x), "v"(dzl_whi.y), "v"(dzl_whi.z), "v"(dzl_whi.w), "v"(dzl_wlo.x), "v"(dzl_wlo.y),
+                         "v"(dzl_wlo.z), "v"(dzl_wlo.w));
+        }
+    }
     // F0: the patches' homographies and the band weights, staged once (plain loads, drained
     // before the ring starts: no global load inside the ring, whose waits count DMA in order)
     float* f0_h = reinterpret_cast<float*>(smem + NBUF * STB);     // [F0_PATCHES][9]
@@ -417,6 +445,54 @@ MARF_DEV void wgrad_dma_body(const WgArgs& a, int chunk_id, int ob, char* smem) 
 #pragma unroll
         for (int q = 0; q < NGF; ++q) t16f[q] = t16_lane(a.ldf, k0 >> 4, KF >> 4, q * 8 + wave < (FB >> 10) ? q * 8 + wave : 0);
     }
+    // DZL: the inputs of stage st's set -- waves 0..3 a quarter of its mask words each, waves 4, 5
+    // half of its g fragments, waves 6, 7 (and every wave past the chunk's end) into the sink, so
+    // that every wave issues one operation per stage
+    auto issue_dzl_in = [&](int st) {
+        const bool real = st < n_st && wave < 6;
+        const size_t set = (size_t)(s_begin >> 5) + (st < n_st ? st : 0);
+        const char* src = wave < 4 ? a.dzl.mk + set * DZL_MK_SET + wave * 256 + lane * 4
+                                   : a.dzl.g + set * DZL_G_SET + (wave & 1) * 256 + lane * 4;
+        const unsigned dst = real ? lds0 + DZL_SM0 + (st % (NBUF + 1)) * DZL_SLOT + wave * 256
+                                  : lds0 + DZL_SM0 + (NBUF + 1) * DZL_SLOT;
+        s2_glds4(src, __builtin_amdgcn_readfirstlane(dst));
+    };
+    // DZL: dz of stage st (row tile `wave` of its 32 pixels) into the dz half of its ring slot, in
+    // two parts so that its latency chain (LDS read -> 2 MFMAs -> mask / pack -> LDS write) does not
+    // stand in front of the stage's product: dzl_mma before it (the product's LDS reads follow with
+    // no LDS write in between), dzl_store after it
+    f32x16 dzl_c = (f32x16){};
+    uint32_t dzl_mw = 0u;
+    auto dzl_mma = [&](int st) {
+        const char* in = smem + DZL_SM0 + (st % (NBUF + 1)) * DZL_SLOT;
+        S2Frag gB;
+        gB.u = lane < 32 ? *reinterpret_cast<const uint4*>(in + DZL_MK_SET + lane * 16) : make_uint4(0, 0, 0, 0);
+        dzl_mw = *reinterpret_cast<const uint32_t*>(in + lane * 16 + (wave >> 1) * 4);
+        dzl_c = (f32x16){};
+        s2_mfma<false>(dzl_c, dzl_whi, gB);
+        s2_mfma<false>(dzl_c, dzl_wlo, gB);
+    };
+    auto dzl_store = [&](int st) {
+        const f32x16& c = dzl_c;
+        const uint32_t mw = dzl_mw;
+        uint32_t hw[8];
+        auto pack = [&](auto rto) {
+            s2_sfor<8>([&](auto qc) {
+                constexpr int q = decltype(qc)::value;
+                float x0, x1;
+                s2_bmask_pair<decltype(rto)::value, q>(mw, c, x0, x1);
+                hw[q] = s2_pk(x0, x1);
+            });
+        };
+        if (wave & 1) pack(std::integral_constant<int, 1>());
+        else pack(std::integral_constant<int, 0>());
+        S2Frag f0, f1;
+        f0.u = make_uint4(hw[0], hw[1], hw[2], hw[3]);
+        f1.u = make_uint4(hw[4], hw[5], hw[6], hw[7]);
+        char* out = smem + (st % NBUF) * STB + t16_lds(lane & 31, 32 * wave + 8 * (lane >> 5), 16);
+        *reinterpret_cast<uint4*>(out) = s2_t16_contig(f0);
+        *reinterpret_cast<uint4*>(out + 1024) = s2_t16_contig(f1);
+    };
     auto issue = [&](int st) {
         const unsigned buf = lds0 + (st % NBUF) * STB;
         const long long row0 = s_begin + (long long)st * SP;
@@ -425,6 +501,7 @@ MARF_DEV void wgrad_dma_body(const WgArgs& a, int chunk_id, int ob, char* smem) 
         const char* f16 = reinterpret_cast<const char*>(a.feat) + (size_t)(row0 >> 5) * (size_t)(a.ldf >> 4) * 1024;
 #pragma unroll
         for (int q = 0; q < NGZ; ++q) {
+            if (dzl) break;                       // (dz is built on chip: dzl_mma / dzl_store)
             const int seg = q * 8 + wave;         // 1 KB = 2 rows per wave instruction
             if constexpr (T16) {
                 glds16(z16 + t16z[q], __builtin_amdgcn_readfirstlane(buf + seg * 1024));
@@ -452,6 +529,18 @@ MARF_DEV void wgrad_dma_body(const WgArgs& a, int chunk_id, int ob, char* smem) 
             }
         }
         if constexpr (F0) compute_f0(st, (st % NBUF) * STB + ZB);  // after the stage's DMA is in flight
+        if constexpr (DZL) {
+            if (dzl) issue_dzl_in(st + 1);  // (the next stage's set: complete when this stage is)
+        }
+    };
+    // the wait for stage st: `ahead` younger stages of PER operations each stay in flight
+    auto ring_wait = [&](int ahead, auto per) {
+        constexpr int PER = decltype(per)::value;
+        if (ahead >= 4) wait_vm<4 * PER>();
+        else if (ahead == 3) wait_vm<3 * PER>();
+        else if (ahead == 2) wait_vm<2 * PER>();
+        else if (ahead == 1) wait_vm<PER>();
+        else wait_vm<0>();
     };
 
     f32x16 acc[RT][CT];
@@ -461,20 +550,35 @@ MARF_DEV void wgrad_dma_body(const WgArgs& a, int chunk_id, int ob, char* smem) 
         for (int j = 0; j < CT; ++j) acc[i][j] = (f32x16){};
     float bsum = 0.f;
 
+    if constexpr (DZL) {
+        if (dzl && n_st > 0) issue_dzl_in(0);  // (older than every stage: no wait counts it)
+    }
     for (int st = 0; st < NBUF - 1 && st < n_st; ++st) issue(st);
     const int g = lane >> 4, gi = lane & 15, q4 = gi >> 2, p4 = gi & 3;
     for (int st = 0; st < n_st; ++st) {
         const int ahead = min(NBUF - 2, n_st - 1 - st);  // stages issued after st, still in flight
-        if (ahead >= 4) wait_vm<4 * PER_ST>();
-        else if (ahead == 3) wait_vm<3 * PER_ST>();
-        else if (ahead == 2) wait_vm<2 * PER_ST>();
-        else if (ahead == 1) wait_vm<PER_ST>();
-        else wait_vm<0>();
+        // (DZL: no dz pieces, one input piece per stage)
+        if (dzl) ring_wait(ahead, std::integral_constant<int, NGF + 1>());
+        else ring_wait(ahead, std::integral_constant<int, PER_ST>());
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         // every wave is past its reads of buffer (st - 1) % NBUF: refill it
         if (st + NBUF - 1 < n_st) issue(st + NBUF - 1);
+        if constexpr (DZL) {
+            if (dzl) {
+                if (st == 0) {  // the first stage's own tile, published by a barrier of its own
+                    dzl_mma(0);
+                    dzl_store(0);
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    __builtin_amdgcn_s_barrier();
+                    asm volatile("" ::: "memory");
+                }
+                // stage st + 1's tile: its inputs arrived with stage st, its slot's last readers
+                // (stage st + 1 - NBUF) are behind this iteration's barrier
+                if (st + 1 < n_st) dzl_mma(st + 1);
+            }
+        }
         if constexpr (F0) {  // the last wave warps the rows of stage st + NBUF (one lane per row)
             if (wave == 7 && lane < SP && st + NBUF < n_st) warp_rows(st + NBUF, lane);
         }
@@ -516,6 +620,11 @@ MARF_DEV void wgrad_dma_body(const WgArgs& a, int chunk_id, int ob, char* smem) 
 #pragma unroll
                 for (int j = 0; j < CT; ++j) acc[i][j] = P::mma32(af[i], bf[j], acc[i][j]);
         }
+        if constexpr (DZL) {
+            // (published by the next iteration's barrier; between the product's two k-steps it
+            //  measured slower: 0.82 against 0.76 ms per launch at C3)
+            if (dzl && st + 1 < n_st) dzl_store(st + 1);
+        }
     }
 
     float* out = a.partial + (size_t)pidx * a.M * a.K + (size_t)m0 * a.K + k0;
@@ -538,7 +647,7 @@ MARF_DEV void wgrad_dma_body(const WgArgs& a, int chunk_id, int ob, char* smem) 
     }
 }
 
-template <class P, int NBUF, int SP, int KF, bool F0 = false, bool T16 = false>
+template <class P, int NBUF, int SP, int KF, bool F0 = false, bool T16 = false, bool DZL = false>
 __global__ __launch_bounds__(512, 1) void k_wgrad_dma(WgArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // (chunk, output block): wider layers (M, K multiples of 256, e.g. 512) split the output in
@@ -554,7 +663,7 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_dma(WgArgs a) {
         chunk_id = blockIdx.x % a.n_chunks;
         ob = blockIdx.x / a.n_chunks;
     }
-    wgrad_dma_body<P, NBUF, SP, KF, F0, T16>(a, chunk_id, ob, smem);
+    wgrad_dma_body<P, NBUF, SP, KF, F0, T16, DZL>(a, chunk_id, ob, smem);
 }
 
 // Last layer (3 outputs): dW[c][k] = sum_px g[px][c] feat[px][k], db[c] = sum_px g[px][c].
@@ -671,11 +780,13 @@ struct WgLayersArgs {
     int n_chunks;
 };
 
-template <class P, int NBUF, int SP, int KF>
+// DZL: a layer whose WgArgs carry dzl.g (layer n-2) rebuilds its dz; one body, the choice is a
+// block-uniform branch inside it (two bodies side by side would spill)
+template <class P, int NBUF, int SP, int KF, bool DZL = false>
 __global__ __launch_bounds__(512, 1) void k_wgrad_dma_layers(WgLayersArgs la) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int l = blockIdx.x / la.n_chunks, c = blockIdx.x - l * la.n_chunks;  // layer-major
-    wgrad_dma_body<P, NBUF, SP, KF, false, true>(la.a[l], c, 0, smem);  // (the step kernel's T16 tensors)
+    wgrad_dma_body<P, NBUF, SP, KF, false, true, DZL>(la.a[l], c, 0, smem);  // (the step kernel's T16 tensors)
 }
 
 struct WgRedJob {
@@ -784,18 +895,22 @@ static bool wgrad_dma_enabled() {
     return !(e && e[0] == '0');
 }
 
-template <class P, int KF, bool F0 = false, bool T16 = false>
+// LDS behind the hidden layers' ring when dz is recomputed: the sets' input slots and their sink
+constexpr size_t WG_DZL_LDS = (size_t)(WG_NBUF_H + 1) * (DZL_MK_SET + DZL_G_SET) + 256;
+
+template <class P, int KF, bool F0 = false, bool T16 = false, bool DZL = false>
 static hipError_t launch_wg_dma(WgArgs a, int n_chunks, hipStream_t s) {
     a.n_chunks = n_chunks;
     a.n_oblk_c = (a.K + KF - 1) / KF;
     constexpr int SP = F0 ? WG_SP0 : KF == 256 ? WG_SPH : 32;
     constexpr int NBUF = KF == 256 ? WG_NBUF_H : F0 ? WG_NBUF_0 : WG_NBUF_96;  // ring depth within 160 KB of LDS
-    const size_t lds = (size_t)NBUF * SP * (512 + KF * 2) + (KF == 256 ? 0 : 1024) + (F0 ? (9 * F0_PATCHES + 32 + (NBUF + 1) * SP * 2) * 4 : 0);
+    const size_t lds = (size_t)NBUF * SP * (512 + KF * 2) + (KF == 256 ? 0 : 1024) + (F0 ? (9 * F0_PATCHES + 32 + (NBUF + 1) * SP * 2) * 4 : 0) +
+                       (DZL ? WG_DZL_LDS : 0);
     {
-        hipError_t e = ensure_dynamic_lds((const void*)k_wgrad_dma<P, NBUF, SP, KF, F0, T16>, lds);
+        hipError_t e = ensure_dynamic_lds((const void*)k_wgrad_dma<P, NBUF, SP, KF, F0, T16, DZL>, lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL((k_wgrad_dma<P, NBUF, SP, KF, F0, T16>), dim3(n_chunks * (a.M / 256) * a.n_oblk_c), dim3(512), lds, s,
+    hipLaunchKernelGGL((k_wgrad_dma<P, NBUF, SP, KF, F0, T16, DZL>), dim3(n_chunks * (a.M / 256) * a.n_oblk_c), dim3(512), lds, s,
                        a);
     return hipGetLastError();
 }
@@ -804,10 +919,15 @@ static hipError_t launch_wg_dma(WgArgs a, int n_chunks, hipStream_t s) {
 // 256x64 (2x1) or 128x64 (1x1).
 hipError_t marf_launch_wgrad(int dtype, const void* dz, int ldz, const void* feat, int ldf, long long S, int M, int K,
                              int chunk, int n_chunks, float* partial, float* bpartial, hipStream_t s,
-                             const WgRange* rng, bool t16) {
+                             const WgRange* rng, bool t16, const WgDzlSrc* dzl) {
     WgArgs a;
     memset(&a, 0, sizeof(a));
     a.t16 = t16 ? 1 : 0;
+    if (dzl && dzl->g) {  // dz recomputed: the one shape marf_wgrad_dzl_ok takes, or an error
+        if (rng || dtype != 1 || !t16 || !dzl->mk || !dzl->w || !marf_wgrad_dzl_ok(M, ldz, K, ldf, S, chunk, n_chunks))
+            return hipErrorInvalidValue;
+        a.dzl = *dzl;
+    }
     if (rng) {
         a.s_lo = rng->s_lo;
         a.s_len = rng->s_len;
@@ -841,6 +961,7 @@ hipError_t marf_launch_wgrad(int dtype, const void* dz, int ldz, const void* fea
     if (rng && (dtype == 0 || !(dma256 || dma96))) return hipErrorInvalidValue;  // range mode: LDS-DMA kernel only
     if (t16 && dtype == 0) return hipErrorInvalidValue;  // (T16: 16-bit tensors of the step kernel only)
     if (dtype == 1) {
+        if (a.dzl.g) return launch_wg_dma<PrecBF16, 256, false, true, true>(a, n_chunks, s);
         if (dma256) return t16 ? launch_wg_dma<PrecBF16, 256, false, true>(a, n_chunks, s) : launch_wg_dma<PrecBF16, 256>(a, n_chunks, s);
         if (dma96) return t16 ? launch_wg_dma<PrecBF16, 96, false, true>(a, n_chunks, s) : launch_wg_dma<PrecBF16, 96>(a, n_chunks, s);
         if (cfg == 0) return launch_wg<PrecBF16, 2, 4>(a, n_chunks, nr * nc, s);
@@ -868,6 +989,11 @@ bool marf_wgrad_range_ok(int dtype, int M, int ldz, int K, int ldf) {
     if (dtype != 1 && dtype != 2) return false;
     if (!(M % 256 == 0 && ldz % 8 == 0 && ldz >= M && wgrad_dma_enabled())) return false;
     return (K % 256 == 0 && ldf % 8 == 0 && ldf >= K) || (K == 96 && ldf == 96);
+}
+
+bool marf_wgrad_dzl_ok(int M, int ldz, int K, int ldf, long long S, int chunk, int n_chunks) {
+    return M == 256 && K == 256 && ldz == 256 && ldf % 8 == 0 && ldf >= K && S % WG_SPH == 0 && chunk % WG_SPH == 0 &&
+           n_chunks >= 1 && wgrad_dma_enabled();
 }
 
 // Layer-0 weight gradient with feat_0 recomputed on chip (step kernel's feat0_recompute); bf16,
@@ -968,6 +1094,7 @@ hipError_t marf_launch_wgrad_fused(const WgFusedLayer* layers, int n_layers, lon
     memset(&la, 0, sizeof(la));
     la.n_chunks = n_chunks;
     int nh = 0;
+    bool any_dzl = false;
     for (int i = 0; i < n_layers; ++i) {
         const WgFusedLayer& Ly = layers[i];
         if (Ly.kind != 0) continue;
@@ -985,17 +1112,27 @@ hipError_t marf_launch_wgrad_fused(const WgFusedLayer* layers, int n_layers, lon
         a.partial = Ly.partial;
         a.bpartial = Ly.bpartial;
         a.t16 = 1;
+        if (Ly.dzl.g) {  // (layer n-2: dz recomputed)
+            if (dtype != 1 || !Ly.dzl.mk || !Ly.dzl.w || !marf_wgrad_dzl_ok(Ly.M, Ly.ldz, Ly.K, Ly.ldf, S, chunk, n_chunks))
+                return hipErrorInvalidValue;
+            a.dzl = Ly.dzl;
+            any_dzl = true;
+        }
     }
     if (nh) {
         const size_t lds = (size_t)WG_NBUF_H * WG_SPH * (512 + 256 * 2);
-        auto go = [&](auto prec) -> hipError_t {
+        auto go = [&](auto prec, auto dzl_tag) -> hipError_t {
             typedef decltype(prec) P;
-            hipError_t er = ensure_dynamic_lds((const void*)k_wgrad_dma_layers<P, WG_NBUF_H, WG_SPH, 256>, lds);
+            constexpr bool DZL = decltype(dzl_tag)::value;
+            const size_t ldsx = lds + (DZL ? WG_DZL_LDS : 0);
+            hipError_t er = ensure_dynamic_lds((const void*)k_wgrad_dma_layers<P, WG_NBUF_H, WG_SPH, 256, DZL>, ldsx);
             if (er != hipSuccess) return er;
-            hipLaunchKernelGGL((k_wgrad_dma_layers<P, WG_NBUF_H, WG_SPH, 256>), dim3(nh * n_chunks), dim3(512), lds, s, la);
+            hipLaunchKernelGGL((k_wgrad_dma_layers<P, WG_NBUF_H, WG_SPH, 256, DZL>), dim3(nh * n_chunks), dim3(512), ldsx, s, la);
             return hipGetLastError();
         };
-        e = dtype == 2 ? go(PrecF16()) : go(PrecBF16());  // (fp16x2: fp16 saved tensors)
+        // (fp16x2: fp16 saved tensors)
+        e = dtype == 2 ? go(PrecF16(), std::false_type())
+                       : (any_dzl ? go(PrecBF16(), std::true_type()) : go(PrecBF16(), std::false_type()));
         if (e != hipSuccess) return e;
     }
     if (l0 && (e = hipStreamWaitEvent(s, join, 0)) != hipSuccess) return e;
