@@ -221,6 +221,44 @@ int marf_masked_mse(const float* d_pred, const float* d_gt, const float* d_mask,
 int marf_masked_mse_backward(const float* d_pred, const float* d_gt, const float* d_mask, int B, int Np,
                              const float* d_denom, const float* d_gout, float* d_dpred, void* stream);
 
+/* Gradient of the masked MSE with respect to a soft (learned, non-binary) mask: Graph.mse_loss's
+ * autograd into `masks` (model/planar.py:388-390, reached from :362-365 when use_implicit_mask).
+ * loss = sum((p - g) m)^2 / (3 sum m), so d loss / d m_q = (2 m_q e_q - 3 loss) / denominator with
+ * e_q = sum_c (p - g)^2.  d_stats: the [loss, denominator, .] triple marf_step_forward / marf_masked_mse
+ * wrote; d_gout: device scalar upstream gradient; d_dmask [B][1][Np].  No host round trip. */
+int marf_masked_mse_mask_backward(const float* d_pred, const float* d_gt, const float* d_mask, int B, int Np,
+                                  const float* d_stats, const float* d_gout, float* d_dmask, void* stream);
+
+/* ---- Implicit mask network (model/planar.py:319-327 construction, :340-352 input and forward,
+ * :475-488 ImplicitMask, :491-518 PosEmbedding).  Per pixel q of patch b the input is
+ * [E[r_q] ; E[g_q] ; E[b_q] ; uv_q]: three rows of the embedding table E [n_vocab][embed_dim]
+ * (embedding_view.weight) chosen by d_index [B][3][Np] (int32; images.rgb[b].long()), and uv =
+ * [x, y, sin(2^k x), sin(2^k y), cos(2^k x), cos(2^k y)]_{k < n_freqs} of the unwarped grid point of the
+ * geometry (grid or canvas; d_H unused).  The MLP is Linear+ReLU x (n_layers - 1), Linear(width, 1),
+ * sigmoid; flat fp32 parameters in module order W0 [width][3 embed_dim + 2 + 4 n_freqs], b0, W1, b1, ...
+ * (mask_mapping.{0,2,..}.{weight,bias}).  dtype: MARF_FP32 only (exact fp32 MFMA); the other recipes
+ * return MARF_ERR_UNSUPPORTED: plain bf16 missed the 1e-2 bound on the weight gradients.
+ * The reference's defaults are embed_dim 128, n_freqs 10, width 256, n_layers 5 (306,945 parameters). */
+typedef struct marf_mask_net marf_mask_net;
+int marf_mask_net_create(int n_vocab, int embed_dim, int n_freqs, int width, int n_layers, int dtype,
+                         marf_mask_net** out);
+void marf_mask_net_destroy(marf_mask_net* net);
+long long marf_mask_net_param_count(const marf_mask_net* net);
+size_t marf_mask_net_packed_bytes(const marf_mask_net* net);
+/* fp32 master parameters -> MFMA operand layouts (after every optimizer step). */
+int marf_mask_net_pack(const marf_mask_net* net, const float* d_params, void* d_packed, void* stream);
+size_t marf_mask_saved_bytes(const marf_mask_net* net, const marf_geometry* geo);
+size_t marf_mask_workspace_bytes(const marf_mask_net* net, const marf_geometry* geo);
+/* m [B][1][Np] (the layout marf_step_forward reads its mask in; var.mask_prediction [B, Np, 1] is the
+ * same memory).  d_saved NULL = inference; else marf_mask_saved_bytes() for the backward. */
+int marf_mask_forward(const marf_mask_net* net, const marf_geometry* geo, const void* d_packed, const float* d_embed,
+                      const int* d_index, float* d_m, void* d_saved, void* stream);
+/* Backward given d loss / d m [B][1][Np]: overwrites d_dparams (flat, fp32).  No gradient for the
+ * embedding table: the reference puts embedding_view in no optimizer group (model/planar.py:93-96),
+ * so layer 0's input gradient is never needed.  d_workspace: marf_mask_workspace_bytes(). */
+int marf_mask_backward(const marf_mask_net* net, const marf_geometry* geo, const void* d_packed, const float* d_m,
+                       const float* d_dm, const void* d_saved, void* d_workspace, float* d_dparams, void* stream);
+
 /* ---- Edge maps (inputs.compute_edges, reference inputs.py:50-67: cv2.Sobel 3x3 CV_64F in x and y,
  * magnitude, cv2.GaussianBlur 5x5 sigma 0, BORDER_REFLECT_101), per channel image on the device.
  * d_img [n_img][H][W] fp32 -> d_out [n_img][H][W] fp64. */

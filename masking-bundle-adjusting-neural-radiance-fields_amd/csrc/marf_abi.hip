@@ -1637,6 +1637,316 @@ int marf_masked_mse_backward(const float* d_pred, const float* d_gt, const float
     return MARF_OK;
 }
 
+int marf_masked_mse_mask_backward(const float* d_pred, const float* d_gt, const float* d_mask, int B, int Np,
+                                  const float* d_stats, const float* d_gout, float* d_dmask, void* stream) {
+    if (B <= 0 || Np <= 0 || !d_pred || !d_gt || !d_mask || !d_stats || !d_gout || !d_dmask)
+        return fail(MARF_ERR_INVALID, "masked_mse_mask_backward: bad args");
+    MarfProfScope ps("loss_mask_bwd", (hipStream_t)stream);
+    HIPCHK(marf_launch_mse_mask_bwd(d_pred, d_gt, d_mask, B, Np, d_stats, d_gout, d_dmask, (hipStream_t)stream),
+           "masked_mse_mask_backward");
+    return MARF_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ implicit mask network
+
+// ImplicitMask + PosEmbedding + embedding_view (model/planar.py:319-327, 475-518): shape and
+// padding plan of the per-pixel mask MLP, in the tile kernels' layouts (marf_common.h)
+struct marf_mask_net {
+    int n_vocab, embed_dim, n_freqs, n_layers, dtype, kdt, elem;
+    int dims[MARF_MAX_LAYERS + 1];
+    int Kp[MARF_MAX_LAYERS], Mp[MARF_MAX_LAYERS], Mt[MARF_MAX_LAYERS];
+    long long w_off[MARF_MAX_LAYERS], b_off[MARF_MAX_LAYERS], param_count;
+    long long wf_off[MARF_MAX_LAYERS], wt_off[MARF_MAX_LAYERS], bias_off[MARF_MAX_LAYERS];
+    size_t packed_bytes, lds;
+    int TP, lda;
+};
+
+struct MaskSavedPlan {
+    size_t feat[MARF_MAX_LAYERS], mask[MARF_MAX_LAYERS], total;
+};
+
+static void plan_mask_saved(const marf_mask_net* n, long long S, MaskSavedPlan& p) {
+    size_t off = 0;
+    for (int l = 0; l < n->n_layers; ++l) {
+        p.feat[l] = off;
+        off += rup((long long)S * n->Kp[l] * n->elem, 256);
+    }
+    p.mask[0] = 0;
+    for (int l = 1; l < n->n_layers; ++l) {
+        p.mask[l] = off;
+        off += rup(S / n->TP * 4096, 256);  // one uint4 per lane per wave per tile
+    }
+    p.total = off;
+}
+
+struct MaskWsPlan {
+    size_t dz[MARF_MAX_LAYERS], glast, part, bpart, total;
+    int chunk, n_chunks, chunk_last, n_chunks_last;
+};
+
+static void plan_mask_ws(const marf_mask_net* n, long long S, MaskWsPlan& p) {
+    size_t off = 0;
+    p.dz[0] = 0;
+    for (int l = 1; l < n->n_layers; ++l) {
+        p.dz[l] = off;
+        off += rup((long long)S * n->Kp[l] * n->elem, 256);
+    }
+    p.glast = off;
+    off += rup(S * 16, 256);
+    long long chunk = rup((S + 255) / 256, 64);
+    if (chunk < 64) chunk = 64;
+    p.chunk = (int)chunk;
+    p.n_chunks = (int)((S + chunk - 1) / chunk);
+    long long cl = rup((S + 1023) / 1024, 64);
+    if (cl < 64) cl = 64;
+    p.chunk_last = (int)cl;
+    p.n_chunks_last = (int)((S + cl - 1) / cl);
+    long long mxo = 0, mxm = 0;
+    for (int l = 0; l < n->n_layers - 1; ++l) {
+        mxo = std::max(mxo, (long long)n->Mp[l] * n->Kp[l]);
+        mxm = std::max(mxm, (long long)n->Mp[l]);
+    }
+    const long long part_elems =
+        std::max((long long)p.n_chunks * mxo, (long long)p.n_chunks_last * 3 * n->Kp[n->n_layers - 1]);
+    const long long bpart_elems = std::max((long long)p.n_chunks * mxm, (long long)p.n_chunks_last * 3);
+    p.part = off;
+    off += rup(part_elems * 4, 256);
+    p.bpart = off;
+    off += rup(bpart_elems * 4, 256);
+    p.total = off;
+}
+
+// the mask net's pixel slots: the crop (or canvas) grid of the step, no homographies needed
+static int make_mask_geo(const marf_geometry* geo, GeoDev& d) {
+    if (!geo) return fail(MARF_ERR_INVALID, "geometry is NULL");
+    if (geo->mode != MARF_GEO_GRID && geo->mode != MARF_GEO_CANVAS)
+        return fail(MARF_ERR_INVALID, "mask net: grid or canvas geometry only (mode %d)", geo->mode);
+    marf_geometry g = *geo;
+    static const float k_unused_H[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
+    g.d_H = k_unused_H;  // (make_geo wants one; the mask kernels never read it)
+    const int rc = make_geo(&g, d, MARF_TILE_PAD);
+    d.Hm = nullptr;
+    return rc;
+}
+
+static void fill_mask_netdev(const marf_mask_net* n, const void* packed, NetDev& d) {
+    memset(&d, 0, sizeof(d));
+    d.n_layers = n->n_layers;
+    d.L = n->n_freqs;
+    d.D = n->dims[0];
+    for (int l = 0; l < n->n_layers; ++l) {
+        d.Kp[l] = n->Kp[l];
+        d.Mp[l] = n->Mp[l];
+        d.Mt[l] = n->Mt[l];
+        d.Wf[l] = (const char*)packed + n->wf_off[l];
+        d.Wt[l] = (const char*)packed + n->wt_off[l];
+        d.bias[l] = (const float*)((const char*)packed + n->bias_off[l]);
+    }
+}
+
+extern "C" {
+
+int marf_mask_net_create(int n_vocab, int embed_dim, int n_freqs, int width, int n_layers, int dtype,
+                         marf_mask_net** out) {
+    if (!out) return fail(MARF_ERR_INVALID, "mask_net_create: NULL argument");
+    *out = nullptr;
+    if (n_vocab < 1) return fail(MARF_ERR_INVALID, "mask_net_create: N_vocab=%d (needs >= 1)", n_vocab);
+    if (embed_dim < 4 || embed_dim % 4)
+        return fail(MARF_ERR_UNSUPPORTED, "mask_net_create: embedding width %d (a positive multiple of 4)", embed_dim);
+    if (n_freqs < 0 || n_freqs > 16) return fail(MARF_ERR_UNSUPPORTED, "mask_net_create: %d frequencies (0..16)", n_freqs);
+    if (n_layers < 2 || n_layers > MARF_MAX_LAYERS)
+        return fail(MARF_ERR_UNSUPPORTED, "mask_net_create: n_layers=%d (supported 2..%d)", n_layers, MARF_MAX_LAYERS);
+    if (width < 32 || width % 32 || width > 512)
+        return fail(MARF_ERR_UNSUPPORTED, "mask_net_create: hidden width %d (a multiple of 32 up to 512)", width);
+    if (dtype != MARF_FP32 && dtype != MARF_BF16 && dtype != MARF_BF16X3 && dtype != MARF_FP16 && dtype != MARF_FP16X2)
+        return fail(MARF_ERR_INVALID, "mask_net_create: dtype %d", dtype);
+    if (dtype != MARF_FP32)
+        return fail(MARF_ERR_UNSUPPORTED,
+                    "mask_net_create: the implicit mask network runs in fp32 only (plain bf16 misses the 1e-2 gradient "
+                    "bound, DESIGN.md); use precision fp32 with use_implicit_mask");
+    const int D = 3 * embed_dim + 2 + 4 * n_freqs;
+    if (rup(D, 32) > 512) return fail(MARF_ERR_UNSUPPORTED, "mask_net_create: layer input %d > 512", D);
+    marf_mask_net* n = new marf_mask_net;
+    memset(n, 0, sizeof(*n));
+    n->n_vocab = n_vocab;
+    n->embed_dim = embed_dim;
+    n->n_freqs = n_freqs;
+    n->n_layers = n_layers;
+    n->dtype = dtype;
+    n->kdt = 0;  // the generic weight-gradient launchers' fp32 kernels
+    n->elem = 4;
+    n->dims[0] = D;
+    for (int l = 1; l < n_layers; ++l) n->dims[l] = width;
+    n->dims[n_layers] = 1;
+    n->Kp[0] = (int)rup(D, 32);
+    for (int l = 0; l < n_layers - 1; ++l) {
+        n->Mp[l] = width;
+        n->Mt[l] = width;
+        n->Kp[l + 1] = width;
+    }
+    n->Mp[n_layers - 1] = 16;
+    n->Mt[n_layers - 1] = n->kdt != 0 ? 16 : 4;
+    const int Kmax = std::max(n->Kp[0], width);
+    n->TP = 64;
+    n->lda = n->kdt != 0 ? Kmax + 8 : Kmax + 1;
+    n->lds = (size_t)n->TP * n->lda * n->elem;
+    if (n->lds + 1024 > 160 * 1024) {
+        delete n;
+        return fail(MARF_ERR_UNSUPPORTED, "mask_net_create: tile does not fit LDS (%zu B)", n->lds);
+    }
+    long long off = 0;
+    size_t boff = 0;
+    for (int l = 0; l < n_layers; ++l) {
+        n->w_off[l] = off;
+        off += (long long)n->dims[l + 1] * n->dims[l];
+        n->b_off[l] = off;
+        off += n->dims[l + 1];
+        n->wf_off[l] = (long long)boff;
+        boff += rup((long long)n->Mp[l] * n->Kp[l] * n->elem, 256);
+        n->wt_off[l] = (long long)boff;
+        boff += rup((long long)n->Kp[l] * n->Mt[l] * n->elem, 256);
+        n->bias_off[l] = (long long)boff;
+        boff += rup((long long)n->Mp[l] * 4, 256);
+    }
+    n->param_count = off;
+    n->packed_bytes = boff;
+    *out = n;
+    return MARF_OK;
+}
+
+void marf_mask_net_destroy(marf_mask_net* net) { delete net; }
+long long marf_mask_net_param_count(const marf_mask_net* net) { return net ? net->param_count : -1; }
+size_t marf_mask_net_packed_bytes(const marf_mask_net* net) { return net ? net->packed_bytes : 0; }
+
+int marf_mask_net_pack(const marf_mask_net* net, const float* d_params, void* d_packed, void* stream) {
+    if (!net || !d_params || !d_packed) return fail(MARF_ERR_INVALID, "mask_net_pack: NULL argument");
+    PackArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n_layers = net->n_layers;
+    long long mx = 0;
+    for (int l = 0; l < net->n_layers; ++l) {
+        PackLayer& p = a.ly[l];
+        p.M = net->dims[l + 1];
+        p.K = net->dims[l];
+        p.Mp = net->Mp[l];
+        p.Kp = net->Kp[l];
+        p.Mt = net->Mt[l];
+        p.w_off = net->w_off[l];
+        p.b_off = net->b_off[l];
+        p.wf_off = net->wf_off[l];
+        p.wt_off = net->wt_off[l];
+        p.bias_off = net->bias_off[l];
+        mx = std::max(mx, (long long)p.Mp * p.Kp + (long long)p.Kp * p.Mt + p.Mp);
+    }
+    MarfProfScope ps("mask_pack_weights", (hipStream_t)stream);
+    HIPCHK(marf_launch_pack(net->kdt, d_params, (char*)d_packed, a, mx, (hipStream_t)stream), "mask_net_pack");
+    return MARF_OK;
+}
+
+size_t marf_mask_saved_bytes(const marf_mask_net* net, const marf_geometry* geo) {
+    GeoDev g;
+    if (!net || make_mask_geo(geo, g) != MARF_OK) return 0;
+    MaskSavedPlan p;
+    plan_mask_saved(net, (long long)g.B * g.Np_pad, p);
+    return p.total;
+}
+
+size_t marf_mask_workspace_bytes(const marf_mask_net* net, const marf_geometry* geo) {
+    GeoDev g;
+    if (!net || make_mask_geo(geo, g) != MARF_OK) return 0;
+    MaskWsPlan p;
+    plan_mask_ws(net, (long long)g.B * g.Np_pad, p);
+    return p.total;
+}
+
+int marf_mask_forward(const marf_mask_net* net, const marf_geometry* geo, const void* d_packed, const float* d_embed,
+                      const int* d_index, float* d_m, void* d_saved, void* stream) {
+    if (!net || !d_packed || !d_embed || !d_index || !d_m) return fail(MARF_ERR_INVALID, "mask_forward: NULL argument");
+    MaskFwdArgs a;
+    memset(&a, 0, sizeof(a));
+    int rc = make_mask_geo(geo, a.geo);
+    if (rc) return rc;
+    fill_mask_netdev(net, d_packed, a.net);
+    a.embed = d_embed;
+    a.index = d_index;
+    a.n_vocab = net->n_vocab;
+    a.embed_dim = net->embed_dim;
+    a.n_freqs = net->n_freqs;
+    a.m = d_m;
+    a.lda = net->lda;
+    const long long S = (long long)a.geo.B * a.geo.Np_pad;
+    if (d_saved) {
+        MaskSavedPlan p;
+        plan_mask_saved(net, S, p);
+        for (int l = 0; l < net->n_layers; ++l) a.feat[l] = (char*)d_saved + p.feat[l];
+        for (int l = 1; l < net->n_layers; ++l) a.mask[l] = (uint64_t*)((char*)d_saved + p.mask[l]);
+    }
+    MarfProfScope ps("mask_fwd", (hipStream_t)stream);
+    HIPCHK(marf_launch_mask_fwd(a, net->lds, (int)(S / net->TP), (hipStream_t)stream), "mask_forward");
+    return MARF_OK;
+}
+
+int marf_mask_backward(const marf_mask_net* net, const marf_geometry* geo, const void* d_packed, const float* d_m,
+                       const float* d_dm, const void* d_saved, void* d_workspace, float* d_dparams, void* stream) {
+    if (!net || !d_packed || !d_m || !d_dm || !d_saved || !d_workspace || !d_dparams)
+        return fail(MARF_ERR_INVALID, "mask_backward: NULL argument");
+    hipStream_t s = (hipStream_t)stream;
+    MaskBwdArgs a;
+    memset(&a, 0, sizeof(a));
+    int rc = make_mask_geo(geo, a.geo);
+    if (rc) return rc;
+    fill_mask_netdev(net, d_packed, a.net);
+    a.m = d_m;
+    a.dm = d_dm;
+    a.lda = net->lda;
+    const long long S = (long long)a.geo.B * a.geo.Np_pad;
+    MaskSavedPlan sp;
+    plan_mask_saved(net, S, sp);
+    MaskWsPlan wp;
+    plan_mask_ws(net, S, wp);
+    char* ws = (char*)d_workspace;
+    const char* sv = (const char*)d_saved;
+    for (int l = 1; l < net->n_layers; ++l) {
+        a.mask[l] = (const uint64_t*)(sv + sp.mask[l]);
+        a.dz[l] = ws + wp.dz[l];
+    }
+    a.glast = (float*)(ws + wp.glast);
+    {
+        MarfProfScope ps("mask_bwd_dgrad", s);
+        HIPCHK(marf_launch_mask_bwd(a, net->lds, (int)(S / net->TP), s), "mask_backward dgrad");
+    }
+    // weight / bias gradients: the generic split-K launchers and their fixed-order reductions
+    float* part = (float*)(ws + wp.part);
+    float* bpart = (float*)(ws + wp.bpart);
+    const int nl = net->n_layers;
+    for (int l = 0; l < nl - 1; ++l) {
+        {
+            MarfProfScope ps(l == 0 ? "mask_wgrad_l0" : "mask_wgrad_hidden", s);
+            HIPCHK(marf_launch_wgrad(net->kdt, ws + wp.dz[l + 1], net->Kp[l + 1], sv + sp.feat[l], net->Kp[l], S,
+                                     net->Mp[l], net->Kp[l], wp.chunk, wp.n_chunks, part, bpart, s),
+                   "mask_backward wgrad");
+        }
+        MarfProfScope ps("mask_wgrad_reduce", s);
+        HIPCHK(marf_launch_wgrad_reduce(part, bpart, wp.n_chunks, net->Mp[l], net->Kp[l], net->dims[l + 1],
+                                        net->dims[l], d_dparams + net->w_off[l], d_dparams + net->b_off[l], s),
+               "mask_backward wgrad reduce");
+    }
+    const int l = nl - 1;
+    {
+        MarfProfScope ps("mask_wgrad_last", s);
+        HIPCHK(marf_launch_wgrad_last(net->kdt, a.glast, sv + sp.feat[l], S, net->Kp[l], net->Kp[l], wp.chunk_last,
+                                      wp.n_chunks_last, part, bpart, s),
+               "mask_backward wgrad last");
+    }
+    // glast rows 1..3 are zero: row 0 of the 3-row partial is the one real output row
+    HIPCHK(marf_launch_wgrad_reduce(part, bpart, wp.n_chunks_last, 3, net->Kp[l], 1, net->dims[l],
+                                    d_dparams + net->w_off[l], d_dparams + net->b_off[l], s),
+           "mask_backward wgrad last reduce");
+    return MARF_OK;
+}
+
 int marf_edge_map(const float* d_img, int n_img, int H, int W, double* d_out, void* stream) {
     if (n_img < 0 || H <= 0 || W <= 0 || (n_img > 0 && (!d_img || !d_out))) return fail(MARF_ERR_INVALID, "edge_map: bad args");
     if (n_img > 65535) return fail(MARF_ERR_INVALID, "edge_map: more than 65535 channel images");

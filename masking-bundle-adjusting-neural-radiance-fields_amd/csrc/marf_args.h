@@ -58,6 +58,31 @@ struct StepArgs {
     int lda;
 };
 
+// Implicit-mask network (marf_mask.hip; reference model/planar.py:340-349, 475-488): the per-pixel
+// input [E[r] ; E[g] ; E[b] ; uv] is built in LDS, the layers run as the tile kernels' do.
+struct MaskFwdArgs {
+    NetDev net;                       // D = 3 * embed_dim + 2 + 4 * n_freqs, Kp[0] = D padded to 32
+    GeoDev geo;                       // crop grid (Hm unused: the mask net sees the unwarped grid)
+    const float* embed;               // [n_vocab][embed_dim] (embedding_view.weight)
+    const int* index;                 // [B][3][Np] vocabulary rows of the three channels
+    int n_vocab, embed_dim, n_freqs;
+    float* m;                         // out: [B][1][Np] sigmoid output
+    void* feat[MARF_MAX_LAYERS];      // saved layer inputs [S][Kp_l] (null: inference)
+    uint64_t* mask[MARF_MAX_LAYERS];  // ReLU mask records of feat_l, l >= 1
+    int lda;
+};
+
+struct MaskBwdArgs {
+    NetDev net;
+    GeoDev geo;
+    const float* m;                         // [B][1][Np] forward output
+    const float* dm;                        // [B][1][Np] upstream gradient
+    const uint64_t* mask[MARF_MAX_LAYERS];  // from the forward
+    void* dz[MARF_MAX_LAYERS];              // out: dz_l, l = 1 .. n-1 [S][Kp_l]
+    float* glast;                           // out: [S][4], rows 1..3 zero
+    int lda;
+};
+
 struct PackLayer {
     int M, K;                            // true dims (nn.Linear weight [M][K])
     int Mp, Kp, Mt;                      // padded: Wf [Mp][Kp], Wt [Kp][Mt], bias [Mp]
@@ -214,6 +239,10 @@ hipError_t marf_launch_wgrad_reduce(const float* partial, const float* bpartial,
                                     int Ko, float* dW, float* db, hipStream_t s, const float* gscale = nullptr,
                                     const float* denom = nullptr, float* scratch = nullptr,
                                     const int* kmap = nullptr, float post = 1.f);
+hipError_t marf_launch_mask_fwd(const marf::MaskFwdArgs& a, size_t lds, int n_tiles, hipStream_t s);
+hipError_t marf_launch_mask_bwd(const marf::MaskBwdArgs& a, size_t lds, int n_tiles, hipStream_t s);
+hipError_t marf_launch_mse_mask_bwd(const float* pred, const float* gt, const float* mask, int B, int Np,
+                                    const float* stats, const float* gout, float* d_mask, hipStream_t s);
 hipError_t marf_launch_mlp_step(const marf::StepArgs& a, int dtype, int TP, int NW, size_t lds, int n_tiles, hipStream_t s);
 hipError_t marf_launch_c2f_weights(const marf::C2fDev& c, int L, float* out, hipStream_t s,
                                    const int* csrc = nullptr, int* cdst = nullptr, int cn = 0);

@@ -81,6 +81,16 @@ _SIGS = {
     "marf_erode_rect": (_c_int, [_c_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_vp, _c_vp]),
     "marf_masked_mse": (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp]),
     "marf_masked_mse_backward": (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp]),
+    "marf_masked_mse_mask_backward": (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp]),
+    "marf_mask_net_create": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_vp)]),
+    "marf_mask_net_destroy": (None, [_c_vp]),
+    "marf_mask_net_param_count": (_c_ll, [_c_vp]),
+    "marf_mask_net_packed_bytes": (_c_sz, [_c_vp]),
+    "marf_mask_net_pack": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp]),
+    "marf_mask_saved_bytes": (_c_sz, [_c_vp, ctypes.POINTER(Geometry)]),
+    "marf_mask_workspace_bytes": (_c_sz, [_c_vp, ctypes.POINTER(Geometry)]),
+    "marf_mask_forward": (_c_int, [_c_vp, ctypes.POINTER(Geometry), _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
+    "marf_mask_backward": (_c_int, [_c_vp, ctypes.POINTER(Geometry), _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
     "marf_adam_step": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_ll, _c_dbl, _c_dbl, _c_dbl, _c_dbl, _c_ll, _c_vp,
                                 _c_vp]),
     "marf_adam_schedule": (_c_int, [_c_dbl, _c_dbl, _c_dbl, _c_ll, _c_ll, _c_vp]),
@@ -617,6 +627,7 @@ class _PlanarStepFunction(torch.autograd.Function):
         geo = engine.grid_geo(Bl, Hm)
         Np = geo_np(engine)
         gt = _f32(gt, "labels").reshape(Bl, 3, Np)
+        ctx.mask_shape = None if mask is None else mask.shape
         mask = None if mask is None else _f32(mask, "masks").reshape(Bl, 1, Np)
         rgb = torch.empty(Bl, Np, 3, device=w.device, dtype=torch.float32)
         stats = torch.empty(3, device=w.device, dtype=torch.float32)
@@ -675,7 +686,14 @@ class _PlanarStepFunction(torch.autograd.Function):
             dw = torch.zeros_like(w)
             dw[ctx.b0:ctx.b1] = dh_local
         grads = _split_grads(dflat, ctx.shapes)
-        return (dw, None, None, None, None, None, None, None, *grads)
+        d_mask = None
+        if ctx.mask is not None and ctx.needs_input_grad[6] and d_loss is not None:
+            # a learned (soft) mask: d (d_loss * loss) / d m from the step's own prediction and stats
+            d_mask = torch.empty_like(ctx.mask)
+            _check(lib().marf_masked_mse_mask_backward(_ptr(rgb), _ptr(ctx.gt), _ptr(ctx.mask), Bl, ctx.mask.shape[2],
+                                                       _ptr(stats), _ptr(gout), _ptr(d_mask), _stream(w)))
+            d_mask = d_mask.view(ctx.mask_shape)
+        return (dw, None, None, None, None, None, d_mask, None, *grads)
 
 
 def render_step(warp_weight, progress, engine, params, gt, mask, denom_override=None, b0=0, b1=None):
@@ -729,6 +747,114 @@ class Engine:
         self.net.pack(flat, self._packed)
         self._packed_version = ver
         return self._packed
+
+
+# ====================================================================== implicit mask network
+
+class MaskNet:
+    """Shape + padding plan of the implicit-mask MLP in the library (marf_mask_net; reference
+    model/planar.py:475-488 ImplicitMask with the :340-349 input).  Planning needs no GPU."""
+
+    def __init__(self, n_vocab, dtype, embed_dim=128, n_freqs=10, width=256, n_layers=5):
+        h = _c_vp()
+        _check(lib().marf_mask_net_create(int(n_vocab), int(embed_dim), int(n_freqs), int(width), int(n_layers),
+                                          int(dtype), ctypes.byref(h)))
+        self._h = h
+        self.n_vocab, self.embed_dim, self.n_freqs = int(n_vocab), int(embed_dim), int(n_freqs)
+        self.width, self.n_layers, self.dtype = int(width), int(n_layers), dtype
+        self.in_dim = 3 * self.embed_dim + 2 + 4 * self.n_freqs
+        self.param_count = lib().marf_mask_net_param_count(h)
+        self.packed_bytes = lib().marf_mask_net_packed_bytes(h)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None) and _lib is not None:
+                _lib.marf_mask_net_destroy(self._h)
+        except Exception:
+            pass
+
+    def pack(self, flat_params, packed):
+        _check(lib().marf_mask_net_pack(self._h, _ptr(flat_params), _ptr(packed), _stream(flat_params)))
+
+    def saved_bytes(self, geo):
+        return lib().marf_mask_saved_bytes(self._h, ctypes.byref(geo))
+
+    def workspace_bytes(self, geo):
+        return lib().marf_mask_workspace_bytes(self._h, ctypes.byref(geo))
+
+
+class MaskEngine:
+    """Library-side state of one ImplicitMask: net plan, packed weights, pixel geometry."""
+
+    def __init__(self, n_vocab, dtype, H, W, patch_H, patch_W, crop=True, **shape):
+        self.net = MaskNet(n_vocab, dtype, **shape)
+        self.H, self.W, self.patch_H, self.patch_W = H, W, patch_H, patch_W
+        self.crop = bool(crop)
+        self._packed = None
+        self._packed_version = None
+
+    def geo(self, B):
+        return grid_geometry(B, self.H, self.W, self.patch_H, self.patch_W, None, self.crop)
+
+    packed_for = Engine.packed_for
+
+
+class _MaskNetFunction(torch.autograd.Function):
+    """ImplicitMask on the [E[r] ; E[g] ; E[b] ; uv] input of every pixel (model/planar.py:340-352):
+    forward gives m [B, Np, 1] (in memory [B][1][Np], the fused step's mask layout), backward takes
+    d m and gives the gradients of the Linear parameters.  The embedding table gets none: the
+    reference trains it in no optimizer group (model/planar.py:93-96)."""
+
+    @staticmethod
+    def forward(ctx, engine, index, embed, *params):
+        embed = _f32(embed, "embedding_view.weight")
+        _dev(index, "mask indices")
+        if index.dtype != torch.int32 or index.dim() != 3 or index.shape[1] != 3:
+            raise TypeError("libmarf: mask indices must be int32 [B, 3, Np]")
+        if embed.shape != (engine.net.n_vocab, engine.net.embed_dim):
+            raise ValueError(f"libmarf: embedding table {tuple(embed.shape)}, expected "
+                             f"{(engine.net.n_vocab, engine.net.embed_dim)}")
+        index = index.contiguous()
+        B, Np = index.shape[0], index.shape[2]
+        geo = engine.geo(B)
+        if Np != geo_np(engine):
+            raise ValueError(f"libmarf: {Np} mask pixels per patch, the geometry has {geo_np(engine)}")
+        packed = engine.packed_for(params)
+        m = torch.empty(B, Np, 1, device=embed.device, dtype=torch.float32)
+        need_grad = any(ctx.needs_input_grad[3:])
+        saved = _BUFS.get("mask_saved", engine.net.saved_bytes(geo), embed.device) if need_grad else None
+        _check(lib().marf_mask_forward(engine.net.handle, ctypes.byref(geo), _ptr(packed), _ptr(embed), _ptr(index),
+                                       _ptr(m), _ptr(saved), _stream(embed)))
+        if need_grad:
+            ctx.save_for_backward(m)
+            ctx.saved_buf, ctx.packed, ctx.engine, ctx.B = saved, packed, engine, B
+            ctx.gen = _BUFS.generation("mask_saved", embed.device)
+        ctx.shapes = [p.shape for p in params]
+        return m
+
+    @staticmethod
+    def backward(ctx, dm):
+        (m,) = ctx.saved_tensors
+        engine = ctx.engine
+        if ctx.gen != _BUFS.generation("mask_saved", m.device):
+            raise RuntimeError("libmarf: the mask net's saved activations were reused by a later forward; "
+                               "call backward() before the next Graph.forward")
+        geo = engine.geo(ctx.B)
+        dm = _f32(dm, "d_mask")
+        ws = _BUFS.get("mask_ws", engine.net.workspace_bytes(geo), m.device)
+        dflat = torch.empty(engine.net.param_count, device=m.device, dtype=torch.float32)
+        _check(lib().marf_mask_backward(engine.net.handle, ctypes.byref(geo), _ptr(ctx.packed), _ptr(m), _ptr(dm),
+                                        _ptr(ctx.saved_buf), _ptr(ws), _ptr(dflat), _stream(m)))
+        return (None, None, None, *_split_grads(dflat, ctx.shapes))
+
+
+def mask_forward(engine, index, embed, params):
+    """m [B, Np, 1] of the implicit-mask net for vocabulary indices [B, 3, Np] (int32)."""
+    return _MaskNetFunction.apply(engine, index, embed, *params)
 
 
 class GradEvents:
@@ -855,7 +981,12 @@ class _MaskedMSE(torch.autograd.Function):
         d = torch.empty_like(pred)
         _check(lib().marf_masked_mse_backward(_ptr(pred), _ptr(gt), _ptr(mask), pred.shape[0], pred.shape[1],
                                               _ptr(out[1:2]), _ptr(gout), _ptr(d), _stream(pred)))
-        return d, None, None, None
+        d_mask = None
+        if mask is not None and ctx.needs_input_grad[2]:  # a learned (soft) mask
+            d_mask = torch.empty_like(mask)
+            _check(lib().marf_masked_mse_mask_backward(_ptr(pred), _ptr(gt), _ptr(mask), pred.shape[0], pred.shape[1],
+                                                       _ptr(out), _ptr(gout), _ptr(d_mask), _stream(pred)))
+        return d, None, d_mask, None
 
 
 def masked_mse(pred_bn3, gt_b3n, mask_b1n=None, denom_override=None):

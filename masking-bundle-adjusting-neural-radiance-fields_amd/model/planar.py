@@ -7,6 +7,9 @@ Same classes, attributes, state-dict keys and training-step order as the referen
                         compute_loss -> edict(render, rgb, mask, edge), mse_loss (:296-391)
   NeuralImageFunction   mlp ModuleList of nn.Linear, progress Parameter, forward(coord_2d),
                         positional_encoding(coord_2d) (:395-471)
+  ImplicitMask          mask_mapping Sequential of nn.Linear / ReLU / Sigmoid (:475-488), PosEmbedding
+                        (:491-518): the learned per-pixel mask of use_implicit_mask, evaluated by
+                        Graph.predict_mask in the library's mask kernels (fp32, one process)
 The arithmetic of the step runs in libmarf.so (marf_hip): Graph.forward is one fused HIP
 prologue+MLP kernel per tile, its backward the dgrad / warp-adjoint / weight-gradient kernels,
 the loss and Adam are HIP kernels too.  Patches shard over ranks (one process per GPU); the
@@ -143,7 +146,9 @@ class Model(torch.nn.Module):
         groups = [dict(params=self.graph.neural_image.parameters(), lr=opt.optim.lr),
                   dict(params=self.graph.warp_param.parameters(), lr=opt.optim.lr_warp)]
         if opt.use_implicit_mask:
-            raise NotImplementedError("the implicit-mask branch is outside this implementation")
+            # the shared mask network at its own rate (model/planar.py:95-96); embedding_view is in
+            # no group, as in the reference: it keeps its random init
+            groups.append(dict(params=self.graph.implicit_mask.parameters(), lr=opt.optim.lr_mask))
         if opt.optim.algo == "Adam":
             self.optim = marf_hip.Adam(groups)
         else:
@@ -219,7 +224,8 @@ class Model(torch.nn.Module):
         """A whole iteration can be captured when it has no host-dependent value per step: one
         process, the fused step, no edge term (its alpha = it / max_iter is a host value), no
         learning-rate scheduler, the library's Adam (its per-step scalars come from a device table)."""
-        return (self.world == 1 and not self.opt.use_edges and self.opt.get("fused_step", True)
+        return (self.world == 1 and not self.opt.use_edges and not self.opt.use_implicit_mask
+                and self.opt.get("fused_step", True)
                 and str(self.opt.device).startswith("cuda") and not self.sched
                 and isinstance(self.optim, marf_hip.Adam))
 
@@ -307,7 +313,7 @@ class Model(torch.nn.Module):
     @staticmethod
     def _drop_autograd(var):
         """Detach the prediction fields of a var bundle (their autograd graph is released)."""
-        for k in ("rgb_prediction", "rgb_prediction_map", "edge_prediction"):
+        for k in ("rgb_prediction", "rgb_prediction_map", "edge_prediction", "mask_prediction", "mask_prediction_map"):
             if torch.is_tensor(var.get(k)):
                 var[k] = var[k].detach()
         var.fused_loss = None
@@ -439,6 +445,9 @@ class Model(torch.nn.Module):
             vals[f"{split}/loss_{key}"] = float(v)
         for key, value in (metric or {}).items():
             vals[f"{split}/{key}"] = float(value)
+        if self.opt.use_implicit_mask and self.images.get("masks") is not None and var.get("mask_prediction_map") is not None:
+            # model/planar.py:237-242: plain MSE of the predicted mask against the loaded one
+            vals[f"{split}/Mask_Error"] = float(self.graph.mse_loss(var.mask_prediction_map, self.images.masks))
         if self.opt.use_homographies and self.images.get("gt_hom") is not None:
             vals[f"{split}/Homography_Error"] = float(self.homography_error(self.gathered_warps(), self.images.gt_hom))
         vals[f"{split}/PSNR"] = -10 * np.log10(vals[f"{split}/loss_rgb"]) if vals.get(f"{split}/loss_rgb") else None
@@ -464,6 +473,18 @@ class Model(torch.nn.Module):
             PIL.Image.fromarray(img).save(f"{self.vis_path}/{self.vis_it}.png")
         except Exception:
             np.save(f"{self.vis_path}/{self.vis_it}.npy", img)
+        if self.opt.use_implicit_mask and var.get("mask_prediction") is not None:
+            # the reference's "implicit_masks" image (model/planar.py:282-286): the B predicted masks side by side
+            B = var.mask_prediction.shape[0]
+            mk = var.mask_prediction.detach().view(B, int(self.graph.h), int(self.graph.w)).clamp(0, 1)
+            mimg = (torch.cat(list(mk), dim=1) * 255).byte().cpu().numpy()
+            try:
+                import PIL.Image
+                PIL.Image.fromarray(mimg).save(f"{self.vis_path}/mask_{self.vis_it}.png")
+            except Exception:
+                np.save(f"{self.vis_path}/mask_{self.vis_it}.npy", mimg)
+            if self.tb:
+                self.tb.add_image(f"{split}/implicit_masks", mimg[None], step)
         self.vis_it += 1
 
 
@@ -485,7 +506,27 @@ class Graph(torch.nn.Module):
         self.max_iter = opt.max_iter
         self.it = 0
         if opt.use_implicit_mask:
-            raise NotImplementedError("the implicit-mask branch is outside this implementation")
+            # model/planar.py:319-327, in this order (the order of the seeded init's RNG draws)
+            if opt.get("build_single_masks"):
+                raise NotImplementedError("build_single_masks: the reference runs those per-patch mask networks on "
+                                          "the CPU and mixes devices (model/planar.py:347); only the shared "
+                                          "implicit mask network is implemented")
+            if _dist() and torch.distributed.get_world_size() > 1:
+                raise NotImplementedError("use_implicit_mask with more than one rank: the learned mask's denominator "
+                                          "3*sum(m) changes every step and would need its own all-reduce before "
+                                          "the backward")
+            if opt.get("cuda_graph"):
+                raise NotImplementedError("cuda_graph with use_implicit_mask: the captured iteration does not cover "
+                                          "the mask network; turn cuda_graph off")
+            if _precision(opt) != marf_hip.MARF_FP32:
+                raise NotImplementedError(f"use_implicit_mask with precision {opt.get('precision')}: the mask "
+                                          "network runs in fp32 only (plain bf16 misses the 1e-2 gradient bound, "
+                                          "DESIGN.md); set precision: fp32")
+            self.embedding_uv = PosEmbedding(10 - 1, 10)
+            self.implicit_mask = ImplicitMask()
+            self.embedding_view = torch.nn.Embedding(int(opt.N_vocab), 128)
+            self._mask_engines = {}
+            self._mask_index = None
         # warp.py:72-80 has the 8-dof sl(3) homography only; "se2" (3 dof: tx, ty, theta) is this
         # implementation's extension (north_star "sl(3)/SE(2)"): its generator is embedded in the
         # sl(3) parameters on the GPU (marf_hip.se2_to_sl3), so every kernel path is shared
@@ -522,18 +563,60 @@ class Graph(torch.nn.Module):
     def _range(self):
         return self.shard if self.shard is not None else (0, self.batch_size)
 
+    # ---- implicit mask (model/planar.py:338-352)
+    def _mask_params(self):
+        """The mask net's Linear parameters as consecutive views of one flat fp32 buffer (one pack,
+        one Adam launch), re-flattened after a device move."""
+        ps = list(self.implicit_mask.parameters())
+        if marf_hip.flat_view(ps) is None:
+            flat = torch.cat([p.detach().reshape(-1) for p in ps]).contiguous()
+            off = 0
+            for p in ps:
+                n = p.numel()
+                p.data = flat[off:off + n].view_as(p)
+                off += n
+        return ps
+
+    def mask_engine(self, device):
+        e = self._mask_engines.get(str(device))
+        if e is None:
+            o = self.opt
+            ph, pw = (o.patch_H, o.patch_W) if o.use_cropped_images else (o.H, o.W)
+            e = marf_hip.MaskEngine(int(o.N_vocab), _precision(o), o.H, o.W, ph, pw, crop=bool(o.use_cropped_images))
+            self._mask_engines[str(device)] = e
+        return e
+
+    def predict_mask(self, rgb):
+        """mask_prediction [B, h*w, 1] for the input images rgb [B, 3, h, w]: vocabulary rows
+        images.rgb[i].long() (:342; the images are floats in [0, 1], so row 1 only where a channel
+        is 1.0), the unwarped grid's uv embedding and the shared ImplicitMask, in one HIP kernel."""
+        key = (rgb.data_ptr(), rgb._version, tuple(rgb.shape))
+        if self._mask_index is None or self._mask_index[0] != key:
+            idx = rgb.long().to(torch.int32).reshape(rgb.shape[0], 3, -1).contiguous()
+            self._mask_index = (key, idx)
+        idx = self._mask_index[1]
+        return marf_hip.mask_forward(self.mask_engine(rgb.device), idx, self.embedding_view.weight.detach(),
+                                     self._mask_params())
+
     def forward(self, var, mode=None):
         b0, b1 = self._range()
         imgs = var.get("images")
         var.fused_loss = None
+        implicit = bool(self.opt.use_implicit_mask) and imgs is not None and imgs.get("rgb") is not None
+        if implicit:
+            var.mask_prediction = self.predict_mask(imgs.rgb)
+            var.mask_prediction_map = var.mask_prediction.view(self.batch_size, int(self.h), int(self.w), 1).permute(0, 3, 1, 2)
         if (torch.is_grad_enabled() and self.opt.get("fused_step", True) and imgs is not None
                 and imgs.get("rgb") is not None and self.opt.loss_weight.render is not None):
             # training forward: the target is known, so the loss and the whole backward are
             # computed in the same pass (marf_step_forward); compute_loss picks the loss up
-            masks = imgs.masks[b0:b1] if imgs.get("masks") is not None else None
+            if implicit:  # the predicted mask replaces images.masks in the rgb loss (:362-365)
+                masks = var.mask_prediction
+            else:
+                masks = imgs.masks[b0:b1] if imgs.get("masks") is not None else None
             denom = self.loss_denominator if self.shard is not None else None
             rgb, loss_rgb = self.neural_image.render_step(self.warp_h(), imgs.rgb[b0:b1], masks, denom, b0, b1)
-            var.fused_loss = (loss_rgb, imgs.rgb, imgs.get("masks"))
+            var.fused_loss = (loss_rgb, imgs.rgb, var.mask_prediction if implicit else imgs.get("masks"))
         else:
             rgb = self.neural_image.render(self.warp_h(), b0, b1)  # [Bl, h*w, 3]
         var.rgb_prediction = rgb
@@ -551,15 +634,23 @@ class Graph(torch.nn.Module):
         b0, b1 = self._range()
         imgs = var.images
         if self.opt.loss_weight.render is not None:
-            masks = imgs.masks[b0:b1] if imgs.get("masks") is not None else None
+            implicit = bool(self.opt.use_implicit_mask)
+            if implicit:  # the learned mask in the rgb term and the edge term (model/planar.py:362-369)
+                masks = var.mask_prediction_map
+            else:
+                masks = imgs.masks[b0:b1] if imgs.get("masks") is not None else None
             fused = var.get("fused_loss")
-            if fused is not None and fused[1] is imgs.rgb and fused[2] is imgs.get("masks"):
+            if fused is not None and fused[1] is imgs.rgb and fused[2] is (var.mask_prediction if implicit
+                                                                           else imgs.get("masks")):
                 rgb_loss = fused[0]  # from the fused training forward (same prediction, target, mask)
             else:
                 rgb_loss = self.mse_loss(var.rgb_prediction_map, imgs.rgb[b0:b1], masks)
             if self.opt.use_edges:
                 if var.get("edge_prediction") is not None and imgs.get("edges") is not None:
-                    me = imgs.masks_eroded[b0:b1] if imgs.get("masks_eroded") is not None else None
+                    if implicit:  # float64 tensor ops below: autograd carries the edge term into m
+                        me = var.mask_prediction_map
+                    else:
+                        me = imgs.masks_eroded[b0:b1] if imgs.get("masks_eroded") is not None else None
                     if self.shard is not None and me is not None and self.edge_denominator is not None:
                         # this rank's share of the global masked MSE: the per-rank terms sum to it
                         diff = (var.edge_prediction - imgs.edges[b0:b1]) * me
@@ -574,7 +665,8 @@ class Graph(torch.nn.Module):
                     edge_loss = torch.zeros((), dtype=torch.float64, device=rgb_loss.device)
             else:
                 edge_loss = torch.tensor(0)
-            mask_loss = torch.tensor(0)
+            # model/planar.py:370: pulls the learned mask towards 1 (weight 0.5 in render)
+            mask_loss = ((1 - var.mask_prediction_map.contiguous()) ** 2).mean() if implicit else torch.tensor(0)
             loss.render = lin_comb([(1 - alpha, rgb_loss), (0.5, mask_loss), (alpha, edge_loss)])
             loss.rgb = rgb_loss
             loss.mask = mask_loss
@@ -597,6 +689,45 @@ class Graph(torch.nn.Module):
         if masks is None:
             return (diff ** 2).mean()
         return ((diff * masks) ** 2).sum() / (masks.sum() * 3)
+
+
+# ============================================================================ implicit mask
+
+class ImplicitMask(torch.nn.Module):
+    """The per-pixel mask MLP (model/planar.py:475-488): latent + in_channels_dir -> W -> W -> W ->
+    W -> 1 with ReLU between the layers and a sigmoid at the end, as `mask_mapping` (state-dict keys
+    mask_mapping.{0,2,4,6,8}.{weight,bias}).  The module holds the parameters; Graph.predict_mask
+    evaluates it, fused with its input formation, in the library (marf_mask_forward)."""
+
+    def __init__(self, latent=3 * 128, W=256, in_channels_dir=42):
+        super().__init__()
+        widths = [latent + in_channels_dir, W, W, W, W]
+        layers = []
+        for k_in, k_out in zip(widths[:-1], widths[1:]):
+            layers += [torch.nn.Linear(k_in, k_out), torch.nn.ReLU(True)]
+        layers += [torch.nn.Linear(W, 1), torch.nn.Sigmoid()]
+        self.mask_mapping = torch.nn.Sequential(*layers)
+
+    def forward(self, x):
+        raise NotImplementedError("ImplicitMask runs fused with its input formation (Graph.predict_mask -> "
+                                  "marf_hip.mask_forward); there is no eager path for an explicit input")
+
+
+class PosEmbedding(torch.nn.Module):
+    """x -> (x, sin(f_0 x), cos(f_0 x), sin(f_1 x), ...) with f_k = 2^k (logscale) or linearly spaced
+    frequencies, no factor pi (model/planar.py:491-518).  Parameter-free; the training path computes
+    the same features inside the mask kernel."""
+
+    def __init__(self, max_logscale, N_freqs, logscale=True):
+        super().__init__()
+        self.funcs = [torch.sin, torch.cos]
+        if logscale:
+            self.freqs = 2 ** torch.linspace(0, max_logscale, N_freqs)
+        else:
+            self.freqs = torch.linspace(1, 2 ** max_logscale, N_freqs)
+
+    def forward(self, x):
+        return torch.cat([x] + [f(freq * x) for freq in self.freqs for f in self.funcs], -1)
 
 
 # ============================================================================ neural image
