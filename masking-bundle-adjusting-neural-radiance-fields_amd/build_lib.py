@@ -24,6 +24,13 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
          "-ffp-contract=off", "-fno-slp-vectorize", "-Wall", "-Wno-unused-function"]
 
 
+# per-unit flags.  marf_step2.hip: MFMAs write their accumulators to the vector half of the register
+# file (hipcc's default at 512 registers per wave is the accumulator half, which the epilogues' VALU
+# cannot read: 16 v_accvgpr_read per row tile); the operand fragments that only MFMAs read go to the
+# accumulator half instead (s2_park).  Register placement only: the same instructions on the same data.
+UNIT_FLAGS = {"marf_step2.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
+
+
 def source_hash():
     """sha1 over the names and contents of csrc/* and include/*.h (what every build compiles)."""
     h = hashlib.sha1()
@@ -72,6 +79,7 @@ def _unit_key(src, cflags):
     marf_abi.hip embeds), its source and every header under csrc/ and include/."""
     h = hashlib.sha1()
     flags = [f for f in cflags if not f.startswith("-DMARF_SOURCE_HASH") or src == "marf_abi.hip"]
+    flags = flags + UNIT_FLAGS.get(src, [])
     h.update(" ".join(flags).encode())
     deps = [os.path.join(HERE, "csrc", src)] + sorted(glob.glob(os.path.join(HERE, "csrc", "*.h")) +
                                                       glob.glob(os.path.join(ROOT, "include", "*.h")))
@@ -111,7 +119,8 @@ def _compile(lib_path, extra, verbose):
             # compiler output to a file, not a pipe: a pipe nobody drains blocks a verbose compile
             log = open(obj + ".log", "w+")
             logs.append(log)
-            procs.append(subprocess.Popen([hipcc] + cflags + ["-c", os.path.join(HERE, "csrc", src), "-o", obj],
+            procs.append(subprocess.Popen([hipcc] + cflags + UNIT_FLAGS.get(src, []) +
+                                          ["-c", os.path.join(HERE, "csrc", src), "-o", obj],
                                           stdout=log, stderr=subprocess.STDOUT))
             while sum(p is not None and p.poll() is None for p in procs) >= jobs:
                 procs[[p is not None and p.poll() is None for p in procs].index(True)].wait()

@@ -70,6 +70,11 @@ MARF_DEV i16x4 s2_tr16(const u16* p) {
     return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) i16x4*)(p));
 }
 
+// An operand fragment that only MFMAs, DS instructions and copies read, pinned to the accumulator
+// half of the register file at this point (MFMA A / B operands may be AGPRs): the vector half then
+// holds what VALU instructions write, and no fragment is copied over before an MFMA
+MARF_DEV void s2_park(S2Frag& f) { asm("" : "+a"(f.f)); }
+
 // 8 floats -> bf16 hi fragment (+ lo remainder fragment)
 template <bool LO>
 MARF_DEV void s2_split8(const float* x, S2Frag& hi, S2Frag& lo) {
@@ -161,6 +166,8 @@ __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Ar
     constexpr bool DZL_OK = SPLIT && !DZ && !HF && C::NMW == 4;
     constexpr int R0Q = NKH / (FIX ? NK0F : NKH);  // layer-0 row tiles per stage (the host's r0)
     constexpr int R0F = R0Q < 1 ? 1 : (R0Q > NRT ? NRT : R0Q);
+    // one wave per SIMD (512 registers): the B operand arrays live in the accumulator half (s2_park)
+    constexpr bool PARK = NW == 4 && FIX;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -892,6 +899,63 @@ __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Ar
 
     const float pi_f = 3.14159265358979323846f;
 
+    // ---- last-layer weight gradient of one pixel set (full-width nets): dW[c][16 ks + i] += r4[c] + lo[c]
+    //      per k-step ks, r4 = one 16x16x32 MFMA from a zero accumulator of A = g^T (the wave's LDS
+    //      image gts, rows 0-2 hi, 4-6 lo) and B = feat^T through the transposing LDS round trip,
+    //      lo = the lo rows' products from the lanes 16 up.  Software-pipelined: the transposing
+    //      write and reads of k-step ks + 1 are issued before the MFMA of ks (the LDS operations of
+    //      one wave execute in order, so the 1 KB buffer is reused with no wait between them), the
+    //      lane shuffles of all k-steps go out together, and the read-modify-writes of the wave's
+    //      wla image are batched under one branch; the waits are the compiler's counted ones.  Every
+    //      element's chain of additions is the one of a serial loop.  post: the fp16x2 recipe's 2^-10.
+    auto dw_last = [&](auto f16_tag, const S2Frag* Bf, float post) {
+        constexpr bool F16 = decltype(f16_tag)::value;
+        // (a compiler barrier: the u16 stores of the image and the 16-B load below do not alias under
+        //  type-based alias analysis)
+        asm volatile("" ::: "memory");
+        const uint4 ga = *reinterpret_cast<const uint4*>(gts + (lane & 15) * 32 + 8 * (lane >> 4));
+        const int gq = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3;
+        const u16* b0 = trs + (8 * gq + q) * 16 + (pp & 1) * 8 + 4 * (pp >> 1);
+        i16x4 vv[2][2];
+        f32x4 r4[NKH];
+        auto round_trip = [&](auto ksc) {
+            constexpr int ks = decltype(ksc)::value;
+            *reinterpret_cast<uint4*>(trs + (pxl * 2 + h) * 8) = Bf[ks].u;
+            asm volatile("" ::: "memory");
+            vv[ks & 1][0] = s2_tr16(b0);
+            vv[ks & 1][1] = s2_tr16(b0 + 4 * 16);
+            asm volatile("" ::: "memory");
+        };
+        round_trip(std::integral_constant<int, 0>());
+        s2_sfor<NKH>([&](auto ksc) {
+            constexpr int ks = decltype(ksc)::value;
+            if constexpr (ks + 1 < NKH) round_trip(std::integral_constant<int, ks + 1>());
+            if constexpr (F16)
+                r4[ks] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, ga), *reinterpret_cast<f16x8*>(vv[ks & 1]), (f32x4){}, 0, 0, 0);
+            else
+                r4[ks] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, ga), *reinterpret_cast<bf16x8*>(vv[ks & 1]), (f32x4){}, 0, 0, 0);
+        });
+        float lo[NKH][3];
+#pragma unroll
+        for (int ks = 0; ks < NKH; ++ks)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) lo[ks][c] = __shfl_down(r4[ks][c], 16, 64);
+        if (lane < 16) {
+            float w[NKH][3];
+#pragma unroll
+            for (int ks = 0; ks < NKH; ++ks)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) w[ks][c] = wla[c * HM + 16 * ks + lane];
+#pragma unroll
+            for (int ks = 0; ks < NKH; ++ks)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    if constexpr (F16) wla[c * HM + 16 * ks + lane] = w[ks][c] + (r4[ks][c] + lo[ks][c]) * post;
+                    else wla[c * HM + 16 * ks + lane] = w[ks][c] + (r4[ks][c] + lo[ks][c]);
+                }
+        }
+    };
+
     // what the dgrad pass keeps of each pixel set's forward: the g operand, the warp's homogeneous
     // point and the tile (-1: no tile; the set's stores go to the sink rows); the rest is recomputed
     struct SetSt {
@@ -1048,6 +1112,10 @@ __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Ar
                 for (int k = 0; k < NKH; ++k) {
                     Bh[k] = Oh[k];
                     Bl[k] = Ol[k];
+                    if constexpr (PARK) {
+                        s2_park(Bh[k]);
+                        s2_park(Bl[k]);
+                    }
                 }
             };
             S2T_BEGIN(5);
@@ -1143,28 +1211,7 @@ __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Ar
                             gts[(4 + c) * 32 + pxl] = f2h(gs - h2f(hi));
                         }
                     }
-                    // (a compiler barrier: the u16 stores and the f16x8 load below do not alias under
-                    //  type-based alias analysis, and without it the second set reused the first set's
-                    //  load of the image)
-                    asm volatile("" ::: "memory");
-                    const f16x8 ga = *reinterpret_cast<const f16x8*>(gts + (lane & 15) * 32 + 8 * (lane >> 4));
-                    const int gq = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3;
-                    const S2Frag* Bf = sset ? Bl : Bh;
-#pragma unroll
-                    for (int ks = 0; ks < NKH; ++ks) {
-                        *reinterpret_cast<uint4*>(trs + (pxl * 2 + h) * 8) = Bf[ks].u;
-                        asm volatile("" ::: "memory");
-                        const u16* b0 = trs + (8 * gq + q) * 16 + (pp & 1) * 8 + 4 * (pp >> 1);
-                        i16x4 vv[2] = {s2_tr16(b0), s2_tr16(b0 + 4 * 16)};
-                        const f32x4 r4 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ga, *reinterpret_cast<f16x8*>(vv), (f32x4){}, 0, 0, 0);
-                        float lo[3];
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) lo[c] = __shfl_down(r4[c], 16, 64);
-                        if (lane < 16) {
-#pragma unroll
-                            for (int c = 0; c < 3; ++c) wla[c * HM + 16 * ks + lane] += (r4[c] + lo[c]) * (1.0f / SC);
-                        }
-                    }
+                    dw_last(F16t(), sset ? Bl : Bh, 1.0f / SC);
                 }
                 SetSt cs;
                 cs.g = Bg;
@@ -1348,6 +1395,10 @@ __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Ar
                 for (int k = 0; k < NKH; ++k) {
                     Bh[k] = Oh[k];
                     if constexpr (SPLIT) Bl[k] = Ol[k];
+                    if constexpr (PARK) {
+                        s2_park(Bh[k]);
+                        if constexpr (SPLIT) s2_park(Bl[k]);
+                    }
                 }
             };
             S2T_BEGIN(14);  // (phase stamps: layer 0 on its own)
@@ -1422,23 +1473,27 @@ __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Ar
                     gts[5 * 32 + pxl] = (u16)(w2 >> 16);
                     gts[6 * 32 + pxl] = (u16)(w3 & 0xffff);
                 }
-                const bf16x8 ga = *reinterpret_cast<const bf16x8*>(gts + (lane & 15) * 32 + 8 * (lane >> 4));
-                const int gq = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3;
-                const int nkl = FIX ? NKH : a.Kl / 16;
-                const int Klw = FIX ? HM : a.Kl;
+                if constexpr (FIX) {
+                    dw_last(BF16t(), Bh, 1.0f);
+                } else {
+                    // (the generic instantiation: a run-time k-step count, one k-step at a time)
+                    const bf16x8 ga = *reinterpret_cast<const bf16x8*>(gts + (lane & 15) * 32 + 8 * (lane >> 4));
+                    const int gq = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3;
+                    const int nkl = a.Kl / 16, Klw = a.Kl;
 #pragma unroll
-                for (int ks = 0; ks < NKH; ++ks) {
-                    if (ks < nkl) {
-                        *reinterpret_cast<uint4*>(trs + (pxl * 2 + h) * 8) = Bh[ks].u;
-                        const u16* b0 = trs + (8 * gq + q) * 16 + (pp & 1) * 8 + 4 * (pp >> 1);
-                        i16x4 vv[2] = {s2_tr16(b0), s2_tr16(b0 + 4 * 16)};
-                        const f32x4 r4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ga, *reinterpret_cast<bf16x8*>(vv), (f32x4){}, 0, 0, 0);
-                        float lo[3];
+                    for (int ks = 0; ks < NKH; ++ks) {
+                        if (ks < nkl) {
+                            *reinterpret_cast<uint4*>(trs + (pxl * 2 + h) * 8) = Bh[ks].u;
+                            const u16* b0 = trs + (8 * gq + q) * 16 + (pp & 1) * 8 + 4 * (pp >> 1);
+                            i16x4 vv[2] = {s2_tr16(b0), s2_tr16(b0 + 4 * 16)};
+                            const f32x4 r4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ga, *reinterpret_cast<bf16x8*>(vv), (f32x4){}, 0, 0, 0);
+                            float lo[3];
 #pragma unroll
-                        for (int c = 0; c < 3; ++c) lo[c] = __shfl_down(r4[c], 16, 64);
-                        if (lane < 16) {
+                            for (int c = 0; c < 3; ++c) lo[c] = __shfl_down(r4[c], 16, 64);
+                            if (lane < 16) {
 #pragma unroll
-                            for (int c = 0; c < 3; ++c) wla[c * Klw + 16 * ks + lane] += r4[c] + lo[c];
+                                for (int c = 0; c < 3; ++c) wla[c * Klw + 16 * ks + lane] += r4[c] + lo[c];
+                            }
                         }
                     }
                 }
@@ -1571,8 +1626,14 @@ __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Ar
             });
 #pragma unroll
             for (int k = 0; k < NKH; ++k) {
-                s2_sfor<NS>([&](auto sc) { Dh[decltype(sc)::value][k] = Do[decltype(sc)::value][k]; });
-                if constexpr (SDZ) Bl[k] = Ol[k];
+                s2_sfor<NS>([&](auto sc) {
+                    Dh[decltype(sc)::value][k] = Do[decltype(sc)::value][k];
+                    if constexpr (PARK) s2_park(Dh[decltype(sc)::value][k]);
+                });
+                if constexpr (SDZ) {
+                    Bl[k] = Ol[k];
+                    if constexpr (PARK) s2_park(Bl[k]);
+                }
             }
         }
         // ---- hidden dgrad chain l = nl-2 .. 1
@@ -1672,8 +1733,14 @@ __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Ar
             });
 #pragma unroll
             for (int k = 0; k < NKH; ++k) {
-                s2_sfor<NS>([&](auto sc) { Dh[decltype(sc)::value][k] = Do[decltype(sc)::value][k]; });
-                if constexpr (SDZ) Bl[k] = Ol[k];
+                s2_sfor<NS>([&](auto sc) {
+                    Dh[decltype(sc)::value][k] = Do[decltype(sc)::value][k];
+                    if constexpr (PARK) s2_park(Dh[decltype(sc)::value][k]);
+                });
+                if constexpr (SDZ) {
+                    Bl[k] = Ol[k];
+                    if constexpr (PARK) s2_park(Bl[k]);
+                }
             }
         }
         // ---- layer-0 dgrad + posenc adjoint: row (tile t, register r) = slot 16 t + r of the

@@ -1,0 +1,98 @@
+"""Small fused-step cases for the step kernel's register placement and instruction order (helper
+module, not a test file; used by test_gpu_step2_sched.py and tools/make_step2_sched_bits.py).
+
+A change of where k_step2's fragments and accumulators live, or of the issue order of independent
+instructions, changes no arithmetic, so every result bit of a step stays what the parent commit's
+library computed.  The cases are the smallest shapes that reach each body of the kernel:
+MARF_STEP2_GRID (read at every launch) caps the persistent grid, so a few blocks take many tiles --
+the last-layer weight gradient accumulates over them in LDS, groups of two tiles and a last single
+tile both occur, and the dgrad runs with a sink set.
+"""
+import hashlib
+import os
+import time
+
+import numpy as np
+import torch
+
+import step_bits
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+BITS_JSON = os.path.join(HERE, "golden", "step2_sched_bits.json")
+DEV = step_bits.DEV
+
+FULL = [256] * 4
+CASES = {
+    # name: (patches, patch_H, patch_W, L, hidden widths, environment, model options)
+    # 32 tiles on 3 blocks (11, 11, 10 tiles): (5, 3) instantiation
+    "acc": (1, 64, 64, 16, FULL, {"MARF_STEP2_GRID": "3"}, {}),
+    # 2,080 pixels per patch: padded pixel slots in each patch's last tile; (3, 2) instantiation
+    "pad-L8": (2, 40, 52, 8, FULL, {"MARF_STEP2_GRID": "2"}, {}),
+    "L10": (1, 64, 64, 10, FULL, {"MARF_STEP2_GRID": "5"}, {}),   # (4, 2)
+    "L13": (1, 64, 64, 13, FULL, {"MARF_STEP2_GRID": "5"}, {}),   # (5, 2)
+    # the generic kernel with an odd row-tile count (96 = 3 x 32)
+    "narrow": (2, 64, 64, 8, [128, 96, 128], {"MARF_STEP2_GRID": "2"}, {}),
+    # the generic kernel on the full-width net (the switch is read at net creation)
+    "generic-full": (1, 64, 64, 16, FULL, {"MARF_STEP2_GRID": "3", "MARF_STEP2_GENERIC": "1"}, {}),
+    # k_step2dz (read at net creation)
+    "dz": (1, 64, 64, 16, FULL, {"MARF_STEP2_GRID": "3", "MARF_STEP2_DZ": "1"}, {}),
+    # k_step2h
+    "fp16x2": (1, 64, 64, 16, FULL, {"MARF_STEP2_GRID": "3"}, {"precision": "fp16x2"}),
+}
+
+
+def build(case, setenv, out="/tmp/marf_sched"):
+    """The seeded model of `case` (as test_gpu_dzl_recompute._build) and its var bundle.
+    setenv(name, value) sets the case's environment before the model is built."""
+    from model import planar
+    from util import EasyDict as edict
+    B, ph, pw, L, hidden, env, over = CASES[case]
+    for k, v in env.items():
+        setenv(k, v)
+    opt = step_bits._opt(out, H=512, W=512, patch_H=ph, patch_W=pw, batch_size=B, use_edges=False,
+                         arch={"layers": [None] + list(hidden) + [3], "skip": [], "posenc": {"L_2D": L}}, **over)
+    torch.manual_seed(3)
+    m = planar.Model(opt)
+    rng = np.random.default_rng(3)
+    yy, xx = np.meshgrid(np.linspace(0, 1, ph), np.linspace(0, 1, pw), indexing="ij")
+    rgb = np.stack([[0.5 + 0.4 * np.sin(2 * np.pi * (rng.uniform(1, 4) * xx + rng.uniform(1, 4) * yy) + rng.uniform(0, 6))
+                     for _ in range(3)] for _ in range(B)]).astype(np.float32)
+    mask = (rng.random((B, 1, ph, pw)) < 0.85).astype(np.float32)
+    warp = (rng.standard_normal((B, 8)) * 0.01).astype(np.float32)
+    mk = torch.from_numpy(mask).to(DEV)
+    m.images = edict(rgb=torch.from_numpy(rgb).to(DEV), masks=mk, masks_eroded=mk, edges=None, gt_hom=None, gt=None)
+    m.build_networks()
+    m.graph.warp_param.weight.data.copy_(torch.from_numpy(warp).to(DEV))
+    m.graph.neural_image.progress.data.fill_(0.2)
+    m.setup_optimizer()
+    m.timer = edict(start=time.time(), it_mean=None)
+    return m, edict(idx=torch.arange(B), images=m.images)
+
+
+def step(m, var):
+    """rgb, loss, every MLP gradient and bias gradient, and d warp of one fused step (the state is
+    left as it was)."""
+    m.optim.zero_grad()
+    v = m.graph.forward(var, mode="train")
+    loss = m.summarize_loss(m.graph.compute_loss(v, mode="train"))
+    loss.all.backward()
+    out = {"rgb": v.rgb_prediction.detach().clone(), "loss": loss.rgb.detach().reshape(1).clone(),
+           "dh": m.graph.warp_param.weight.grad.detach().clone()}
+    for i, lay in enumerate(m.graph.neural_image.mlp):
+        out[f"dW{i}"] = lay.weight.grad.detach().clone()
+        out[f"db{i}"] = lay.bias.grad.detach().clone()
+    return out
+
+
+def digest(t):
+    a = t.detach().contiguous().cpu()
+    return hashlib.sha1(a.view(torch.uint8).numpy().tobytes()).hexdigest()
+
+
+def case_bits(case, setenv):
+    """{"kernel": the step kernel's name, "bits": {tensor: sha1 of its bytes}} of one step of `case`."""
+    m, var = build(case, setenv)
+    kernel = m.graph.neural_image.engine(torch.device(DEV)).net.step_kernel
+    out = step(m, var)
+    assert all(torch.isfinite(v).all() for v in out.values()), case
+    return {"kernel": kernel, "bits": {k: digest(v) for k, v in out.items()}}
