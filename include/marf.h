@@ -48,6 +48,12 @@ extern "C" {
                          nets (5 layers, every hidden layer 256 wide, 8 <= L <= 16, no skip); fused step and
                          marf_render only */
 
+#define MARF_BF16X3A 5 /* the mask network's all-operands-split bf16 (marf_mask_net_create only; marf_net_create*
+                          return MARF_ERR_UNSUPPORTED): every GEMM operand x -- weights, activations, dz -- is
+                          hi = bf16_rne(x), lo = bf16_rne(x - hi), every product hi*hi + hi*lo + lo*hi into one fp32
+                          accumulator (v_mfma_f32_32x32x16_bf16), in the forward, the dgrad and the weight gradient;
+                          saved tensors as hi and lo bf16 planes (the fp32 recipe's bytes per pixel) */
+
 #define MARF_GEO_GRID 0   /* pixels of the centre crop, warped by a per-patch homography */
 #define MARF_GEO_COORDS 1 /* explicit [n][2] coordinates (one point set) */
 #define MARF_GEO_CANVAS 2 /* every pixel of the H x W canvas (use_cropped_images off), warped per patch
@@ -236,8 +242,12 @@ int marf_masked_mse_mask_backward(const float* d_pred, const float* d_gt, const 
  * [x, y, sin(2^k x), sin(2^k y), cos(2^k x), cos(2^k y)]_{k < n_freqs} of the unwarped grid point of the
  * geometry (grid or canvas; d_H unused).  The MLP is Linear+ReLU x (n_layers - 1), Linear(width, 1),
  * sigmoid; flat fp32 parameters in module order W0 [width][3 embed_dim + 2 + 4 n_freqs], b0, W1, b1, ...
- * (mask_mapping.{0,2,..}.{weight,bias}).  dtype: MARF_FP32 only (exact fp32 MFMA); the other recipes
- * return MARF_ERR_UNSUPPORTED: plain bf16 missed the 1e-2 bound on the weight gradients.
+ * (mask_mapping.{0,2,..}.{weight,bias}).  dtype: MARF_FP32 (exact fp32 MFMA) or MARF_BF16X3A (every operand
+ * split into bf16 hi + lo; ~1e-5 of max on the gradients); MARF_BF16 / BF16X3 / FP16 / FP16X2 return
+ * MARF_ERR_UNSUPPORTED: plain bf16 missed the 1e-2 bound on the weight gradients and the image net's single-bf16
+ * dz sits on it.  MARF_BF16X3A packs each matrix as a hi and a lo bf16 image (packed_bytes: two
+ * bf16 planes per matrix); its saved / workspace buffers hold hi and lo [S][Kp] bf16 planes per tensor and are
+ * as large as the fp32 recipe's.
  * The reference's defaults are embed_dim 128, n_freqs 10, width 256, n_layers 5 (306,945 parameters). */
 typedef struct marf_mask_net marf_mask_net;
 int marf_mask_net_create(int n_vocab, int embed_dim, int n_freqs, int width, int n_layers, int dtype,

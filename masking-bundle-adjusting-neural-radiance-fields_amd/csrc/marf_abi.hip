@@ -380,6 +380,10 @@ int marf_net_create_skip(int n_layers, const int* dims, int L, int dtype, long l
     *out = nullptr;
     if (n_layers < 2 || n_layers > MARF_MAX_LAYERS)
         return fail(MARF_ERR_UNSUPPORTED, "net_create: n_layers=%d (supported 2..%d)", n_layers, MARF_MAX_LAYERS);
+    if (dtype == MARF_BF16X3A)
+        return fail(MARF_ERR_UNSUPPORTED,
+                    "net_create: MARF_BF16X3A is a mask-network recipe (marf_mask_net_create); the image network takes "
+                    "MARF_FP32, MARF_BF16, MARF_BF16X3, MARF_FP16 or MARF_FP16X2");
     if (dtype != MARF_FP32 && dtype != MARF_BF16 && dtype != MARF_BF16X3 && dtype != MARF_FP16 && dtype != MARF_FP16X2)
         return fail(MARF_ERR_INVALID, "net_create: dtype %d", dtype);
     if (L < 0 || L > 32) return fail(MARF_ERR_UNSUPPORTED, "net_create: L=%d (supported 0..32)", L);
@@ -1654,7 +1658,9 @@ int marf_masked_mse_mask_backward(const float* d_pred, const float* d_gt, const 
 // ImplicitMask + PosEmbedding + embedding_view (model/planar.py:319-327, 475-518): shape and
 // padding plan of the per-pixel mask MLP, in the tile kernels' layouts (marf_common.h)
 struct marf_mask_net {
-    int n_vocab, embed_dim, n_freqs, n_layers, dtype, kdt, elem;
+    // kdt: arithmetic of the generic weight-gradient launchers (0 fp32, 1 bf16); split: MARF_BF16X3A, every
+    // operand and saved tensor as two bf16 planes (hi, lo) -- elem stays 4 bytes per stored value
+    int n_vocab, embed_dim, n_freqs, n_layers, dtype, kdt, elem, split;
     int dims[MARF_MAX_LAYERS + 1];
     int Kp[MARF_MAX_LAYERS], Mp[MARF_MAX_LAYERS], Mt[MARF_MAX_LAYERS];
     long long w_off[MARF_MAX_LAYERS], b_off[MARF_MAX_LAYERS], param_count;
@@ -1760,9 +1766,10 @@ int marf_mask_net_create(int n_vocab, int embed_dim, int n_freqs, int width, int
         return fail(MARF_ERR_UNSUPPORTED, "mask_net_create: n_layers=%d (supported 2..%d)", n_layers, MARF_MAX_LAYERS);
     if (width < 32 || width % 32 || width > 512)
         return fail(MARF_ERR_UNSUPPORTED, "mask_net_create: hidden width %d (a multiple of 32 up to 512)", width);
-    if (dtype != MARF_FP32 && dtype != MARF_BF16 && dtype != MARF_BF16X3 && dtype != MARF_FP16 && dtype != MARF_FP16X2)
+    if (dtype != MARF_FP32 && dtype != MARF_BF16 && dtype != MARF_BF16X3 && dtype != MARF_FP16 && dtype != MARF_FP16X2 &&
+        dtype != MARF_BF16X3A)
         return fail(MARF_ERR_INVALID, "mask_net_create: dtype %d", dtype);
-    if (dtype != MARF_FP32)
+    if (dtype != MARF_FP32 && dtype != MARF_BF16X3A)
         return fail(MARF_ERR_UNSUPPORTED,
                     "mask_net_create: the implicit mask network runs in fp32 only (plain bf16 misses the 1e-2 gradient "
                     "bound, DESIGN.md); use precision fp32 with use_implicit_mask");
@@ -1775,8 +1782,9 @@ int marf_mask_net_create(int n_vocab, int embed_dim, int n_freqs, int width, int
     n->n_freqs = n_freqs;
     n->n_layers = n_layers;
     n->dtype = dtype;
-    n->kdt = 0;  // the generic weight-gradient launchers' fp32 kernels
-    n->elem = 4;
+    n->split = dtype == MARF_BF16X3A;
+    n->kdt = n->split ? 1 : 0;  // fp32: the generic weight-gradient launchers' fp32 kernels
+    n->elem = 4;                // (split: a bf16 hi + lo pair per value)
     n->dims[0] = D;
     for (int l = 1; l < n_layers; ++l) n->dims[l] = width;
     n->dims[n_layers] = 1;
@@ -1841,7 +1849,7 @@ int marf_mask_net_pack(const marf_mask_net* net, const float* d_params, void* d_
         mx = std::max(mx, (long long)p.Mp * p.Kp + (long long)p.Kp * p.Mt + p.Mp);
     }
     MarfProfScope ps("mask_pack_weights", (hipStream_t)stream);
-    HIPCHK(marf_launch_pack(net->kdt, d_params, (char*)d_packed, a, mx, (hipStream_t)stream), "mask_net_pack");
+    HIPCHK(marf_launch_pack(net->split ? 3 : net->kdt, d_params, (char*)d_packed, a, mx, (hipStream_t)stream), "mask_net_pack");
     return MARF_OK;
 }
 
@@ -1876,6 +1884,7 @@ int marf_mask_forward(const marf_mask_net* net, const marf_geometry* geo, const 
     a.n_freqs = net->n_freqs;
     a.m = d_m;
     a.lda = net->lda;
+    a.split = net->split;
     const long long S = (long long)a.geo.B * a.geo.Np_pad;
     if (d_saved) {
         MaskSavedPlan p;
@@ -1901,6 +1910,7 @@ int marf_mask_backward(const marf_mask_net* net, const marf_geometry* geo, const
     a.m = d_m;
     a.dm = d_dm;
     a.lda = net->lda;
+    a.split = net->split;
     const long long S = (long long)a.geo.B * a.geo.Np_pad;
     MaskSavedPlan sp;
     plan_mask_saved(net, S, sp);
@@ -1924,9 +1934,18 @@ int marf_mask_backward(const marf_mask_net* net, const marf_geometry* geo, const
     for (int l = 0; l < nl - 1; ++l) {
         {
             MarfProfScope ps(l == 0 ? "mask_wgrad_l0" : "mask_wgrad_hidden", s);
-            HIPCHK(marf_launch_wgrad(net->kdt, ws + wp.dz[l + 1], net->Kp[l + 1], sv + sp.feat[l], net->Kp[l], S,
-                                     net->Mp[l], net->Kp[l], wp.chunk, wp.n_chunks, part, bpart, s),
-                   "mask_backward wgrad");
+            if (net->split) {  // hi plane [S][Kp], the lo plane behind it
+                const char* dzp = ws + wp.dz[l + 1];
+                const char* ftp = sv + sp.feat[l];
+                HIPCHK(marf_launch_wgrad_split(dzp, dzp + (size_t)S * net->Kp[l + 1] * 2, net->Kp[l + 1], ftp,
+                                               ftp + (size_t)S * net->Kp[l] * 2, net->Kp[l], S, net->Mp[l], net->Kp[l],
+                                               wp.chunk, wp.n_chunks, part, bpart, s),
+                       "mask_backward wgrad");
+            } else {
+                HIPCHK(marf_launch_wgrad(net->kdt, ws + wp.dz[l + 1], net->Kp[l + 1], sv + sp.feat[l], net->Kp[l], S,
+                                         net->Mp[l], net->Kp[l], wp.chunk, wp.n_chunks, part, bpart, s),
+                       "mask_backward wgrad");
+            }
         }
         MarfProfScope ps("mask_wgrad_reduce", s);
         HIPCHK(marf_launch_wgrad_reduce(part, bpart, wp.n_chunks, net->Mp[l], net->Kp[l], net->dims[l + 1],
@@ -1936,7 +1955,8 @@ int marf_mask_backward(const marf_mask_net* net, const marf_geometry* geo, const
     const int l = nl - 1;
     {
         MarfProfScope ps("mask_wgrad_last", s);
-        HIPCHK(marf_launch_wgrad_last(net->kdt, a.glast, sv + sp.feat[l], S, net->Kp[l], net->Kp[l], wp.chunk_last,
+        // (split: feat_{n-1} was saved as fp32, float(hi) + float(lo): the fp32 kernel serves both recipes)
+        HIPCHK(marf_launch_wgrad_last(0, a.glast, sv + sp.feat[l], S, net->Kp[l], net->Kp[l], wp.chunk_last,
                                       wp.n_chunks_last, part, bpart, s),
                "mask_backward wgrad last");
     }

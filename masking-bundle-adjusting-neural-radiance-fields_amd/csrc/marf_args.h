@@ -70,6 +70,7 @@ struct MaskFwdArgs {
     void* feat[MARF_MAX_LAYERS];      // saved layer inputs [S][Kp_l] (null: inference)
     uint64_t* mask[MARF_MAX_LAYERS];  // ReLU mask records of feat_l, l >= 1
     int lda;
+    int split;                        // MARF_BF16X3A: two bf16 planes (hi, lo) per operand and saved tensor
 };
 
 struct MaskBwdArgs {
@@ -81,6 +82,7 @@ struct MaskBwdArgs {
     void* dz[MARF_MAX_LAYERS];              // out: dz_l, l = 1 .. n-1 [S][Kp_l]
     float* glast;                           // out: [S][4], rows 1..3 zero
     int lda;
+    int split;                              // MARF_BF16X3A (dz_l: hi plane [S][Kp_l], then the lo plane)
 };
 
 struct PackLayer {
@@ -233,6 +235,11 @@ hipError_t marf_launch_wgrad_fused(const WgFusedLayer* layers, int n_layers, lon
                                    const GeoDev& f0_geo, const float* c2f_w, int L, int nk0, const float* gscale,
                                    const float* denom, hipStream_t s, hipStream_t s2, hipEvent_t fork, hipEvent_t join,
                                    int dtype = 1, float post = 1.f);  // dtype 2 / post 2^-10: the fp16x2 recipe
+// MARF_BF16X3A (the mask net): dW = dz_h^T a_h + dz_h^T a_l + dz_l^T a_h, db = sum (dz_h + dz_l), each
+// operand given as its hi and lo [S][ld] bf16 planes; the same [n_chunks][M][K] partials as marf_launch_wgrad
+hipError_t marf_launch_wgrad_split(const void* dz_hi, const void* dz_lo, int ldz, const void* feat_hi,
+                                   const void* feat_lo, int ldf, long long S, int M, int K, int chunk, int n_chunks,
+                                   float* partial, float* bpartial, hipStream_t s);
 hipError_t marf_launch_wgrad_last(int dtype, const float* glast, const void* feat, long long S, int ldf, int K,
                                   int chunk, int n_chunks, float* partial, float* bpartial, hipStream_t s);
 hipError_t marf_launch_wgrad_reduce(const float* partial, const float* bpartial, int n_chunks, int M, int K, int Mo,
@@ -262,6 +269,7 @@ hipError_t marf_launch_adam(float* p, const float* g, float* m, float* v, long l
 hipError_t marf_launch_adam_sched(float* p, const float* g, float* m, float* v, long long n, float w1, float b2,
                                   float one_minus_b2, const float* sched, const int* index, float eps,
                                   const float* grad_scale, hipStream_t s);
+// dtype 3: the all-operands-split bf16 images (hi [rows][K], then lo, per matrix)
 hipError_t marf_launch_pack(int dtype, const float* params, char* packed, const marf::PackArgs& a,
                             long long max_elems, hipStream_t s);
 hipError_t marf_launch_pixel_grid(const GeoDev& g, float* xy, int n, hipStream_t s);

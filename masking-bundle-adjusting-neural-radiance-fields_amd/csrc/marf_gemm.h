@@ -629,4 +629,255 @@ MARF_DEV void warp_adjoint(const NetDev& net, const GeoDev& geo, int c2f_on, con
     }
 }
 
+// ======================================================================== all-operands-split bf16
+//
+// The mask network's MARF_BF16X3A recipe: every GEMM operand x is the pair hi = bf16_rne(x),
+// lo = bf16_rne(x - float(hi)), and every product is hi*hi + hi*lo + lo*hi into one fp32 accumulator
+// (lo*lo dropped).  Each operand lives in two planes of the same shape: the LDS tile [TP][lda] twice
+// (lo at +TP*lda elements), the fragment-major weight image twice (lo at +rows*K elements).
+
+// x0..x3 split into 4 hi and 4 lo bf16 (two packed RNE conversions per plane)
+MARF_DEV void split4(float x0, float x1, float x2, float x3, uint2& hi, uint2& lo) {
+    hi.x = PrecBF16::pk2(x0, x1);
+    hi.y = PrecBF16::pk2(x2, x3);
+    const float r0 = x0 - __uint_as_float(hi.x << 16), r1 = x1 - __uint_as_float(hi.x & 0xffff0000u);
+    const float r2 = x2 - __uint_as_float(hi.y << 16), r3 = x3 - __uint_as_float(hi.y & 0xffff0000u);
+    lo.x = PrecBF16::pk2(r0, r1);
+    lo.y = PrecBF16::pk2(r2, r3);
+}
+MARF_DEV void split1(float x, u16& hi, u16& lo) {
+    hi = f2bf(x);
+    lo = f2bf(x - bf2f(hi));
+}
+MARF_DEV void store4_split(u16* dh, u16* dl, float x0, float x1, float x2, float x3) {
+    uint2 hi, lo;
+    split4(x0, x1, x2, x3, hi, lo);
+    *reinterpret_cast<uint2*>(dh) = hi;
+    *reinterpret_cast<uint2*>(dl) = lo;
+}
+
+// gemm_rows with both operands split: per k-step the A fragments hi + lo (the L2 register ring) and
+// the B fragments hi + lo (LDS, two named buffers), 3 NA PT MFMAs into the same accumulators, the
+// three terms outermost so NA PT independent MFMAs stand between two on one accumulator.  The issue
+// order is pinned as in gemm_rows; the ring is 4 deep for NA <= 2, 2 deep above (register budget).
+template <int NA, int RT, int PT, int NW = 4>
+MARF_DEV void gemm_rows_split(f32x16 (&acc)[RT][PT], const u16* __restrict__ Wh, const u16* __restrict__ Wl, int K,
+                              const u16* acth, const u16* actl, int lda, int wave, int lane, const float* bias) {
+    typedef PrecBF16 P;
+    typedef P::frag F;
+    const int ko = P::kofs(lane);
+    const int rl = lane & 31;
+    const int nk = K / P::KS;
+    // the accumulators start at the bias of their output row (set here, inside the NA dispatch: set
+    // before it, the start values stayed live beside the accumulators through every case and spilled)
+    if (bias) {
+#pragma unroll
+        for (int i = 0; i < NA; ++i) {
+            const float* bb = bias + (wave + NW * i) * 32 + 4 * (lane >> 5);
+            f32x16 init;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float4 bv = *reinterpret_cast<const float4*>(bb + 8 * q);
+                init[4 * q] = bv.x;
+                init[4 * q + 1] = bv.y;
+                init[4 * q + 2] = bv.z;
+                init[4 * q + 3] = bv.w;
+            }
+#pragma unroll
+            for (int j = 0; j < PT; ++j) acc[i][j] = init;
+        }
+    }
+    size_t wofs[NA];
+#pragma unroll
+    for (int i = 0; i < NA; ++i) wofs[i] = ((size_t)(wave + NW * i) * nk * 64 + lane) * P::FE;
+    const size_t bofs = (size_t)rl * lda + ko;
+    auto ldA = [&](F (&dh)[NA], F (&dl)[NA], int k) {
+        const int kc = (k < nk ? k : nk - 1) * 64 * P::FE;
+#pragma unroll
+        for (int i = 0; i < NA; ++i) {
+            dh[i] = P::load_frag(Wh + wofs[i] + kc);
+            dl[i] = P::load_frag(Wl + wofs[i] + kc);
+        }
+    };
+    auto ldB = [&](F (&dh)[PT], F (&dl)[PT], int k) {
+        const int kc = (k < nk ? k : nk - 1) * P::KS;
+#pragma unroll
+        for (int j = 0; j < PT; ++j) {
+            dh[j] = P::load_frag(acth + bofs + (size_t)j * 32 * lda + kc);
+            dl[j] = P::load_frag(actl + bofs + (size_t)j * 32 * lda + kc);
+        }
+    };
+    auto mma = [&](const F (&ah)[NA], const F (&al)[NA], const F (&bh)[PT], const F (&bl)[PT]) {
+#pragma unroll
+        for (int j = 0; j < PT; ++j)
+#pragma unroll
+            for (int i = 0; i < NA; ++i) acc[i][j] = P::mma32(ah[i], bh[j], acc[i][j]);
+#pragma unroll
+        for (int j = 0; j < PT; ++j)
+#pragma unroll
+            for (int i = 0; i < NA; ++i) acc[i][j] = P::mma32(ah[i], bl[j], acc[i][j]);
+#pragma unroll
+        for (int j = 0; j < PT; ++j)
+#pragma unroll
+            for (int i = 0; i < NA; ++i) acc[i][j] = P::mma32(al[i], bh[j], acc[i][j]);
+    };
+    F A0h[NA], A0l[NA], A1h[NA], A1l[NA], B0h[PT], B0l[PT], B1h[PT], B1l[PT];
+    if constexpr (NA > 2) {
+        ldA(A0h, A0l, 0);
+        ldA(A1h, A1l, 1);
+        ldB(B0h, B0l, 0);
+        int k = 0;
+        for (; k + 2 <= nk; k += 2) {
+            ldB(B1h, B1l, k + 1);
+            __builtin_amdgcn_sched_barrier(0);
+            mma(A0h, A0l, B0h, B0l);
+            __builtin_amdgcn_sched_barrier(0);
+            ldA(A0h, A0l, k + 2);
+            ldB(B0h, B0l, k + 2);
+            __builtin_amdgcn_sched_barrier(0);
+            mma(A1h, A1l, B1h, B1l);
+            __builtin_amdgcn_sched_barrier(0);
+            ldA(A1h, A1l, k + 3);
+        }
+        if (k < nk) mma(A0h, A0l, B0h, B0l);
+    } else {
+        F A2h[NA], A2l[NA], A3h[NA], A3l[NA];
+        ldA(A0h, A0l, 0);
+        ldA(A1h, A1l, 1);
+        ldA(A2h, A2l, 2);
+        ldA(A3h, A3l, 3);
+        ldB(B0h, B0l, 0);
+        int k = 0;
+        for (; k + 4 <= nk; k += 4) {
+            ldB(B1h, B1l, k + 1);
+            __builtin_amdgcn_sched_barrier(0);
+            mma(A0h, A0l, B0h, B0l);
+            __builtin_amdgcn_sched_barrier(0);
+            ldA(A0h, A0l, k + 4);
+            ldB(B0h, B0l, k + 2);
+            __builtin_amdgcn_sched_barrier(0);
+            mma(A1h, A1l, B1h, B1l);
+            __builtin_amdgcn_sched_barrier(0);
+            ldA(A1h, A1l, k + 5);
+            ldB(B1h, B1l, k + 3);
+            __builtin_amdgcn_sched_barrier(0);
+            mma(A2h, A2l, B0h, B0l);
+            __builtin_amdgcn_sched_barrier(0);
+            ldA(A2h, A2l, k + 6);
+            ldB(B0h, B0l, k + 4);
+            __builtin_amdgcn_sched_barrier(0);
+            mma(A3h, A3l, B1h, B1l);
+            __builtin_amdgcn_sched_barrier(0);
+            ldA(A3h, A3l, k + 7);
+        }
+        // remainder (nk % 4 steps): A0..A2 hold steps k..k+2, B0 holds step k
+        if (k < nk) {
+            ldB(B1h, B1l, k + 1);
+            mma(A0h, A0l, B0h, B0l);
+            if (k + 1 < nk) {
+                ldB(B0h, B0l, k + 2);
+                mma(A1h, A1l, B1h, B1l);
+                if (k + 2 < nk) mma(A2h, A2l, B0h, B0l);
+            }
+        }
+    }
+}
+
+// gemm_tile of the split recipe: the wave's row tiles dispatched once per layer, bias as the
+// accumulators' start.  W: the hi image of rows x K elements, the lo image right behind it.  The saved
+// tile's stores (two planes) go out after the GEMM, as in gemm_tile.
+template <int RT, int PT, int NW = 4>
+MARF_DEV void gemm_tile_split(f32x16 (&acc)[RT][PT], const u16* __restrict__ W, int rows, int K, const u16* acth,
+                              const u16* actl, int lda, int wave, int lane, const float* bias, TileStore<u16>& sth,
+                              TileStore<u16>& stl) {
+    const int n_rt = rows / 32;
+#pragma unroll
+    for (int i = 0; i < RT; ++i)
+#pragma unroll
+        for (int j = 0; j < PT; ++j) acc[i][j] = (f32x16){};
+    int na = (n_rt - wave + NW - 1) / NW;
+    na = na < 0 ? 0 : (na > RT ? RT : na);
+    const u16* Wl = W + (size_t)rows * K;
+    switch (na) {
+        case 1: gemm_rows_split<1, RT, PT, NW>(acc, W, Wl, K, acth, actl, lda, wave, lane, bias); break;
+        case 2: gemm_rows_split<2, RT, PT, NW>(acc, W, Wl, K, acth, actl, lda, wave, lane, bias); break;
+        case 3: if constexpr (RT >= 3) gemm_rows_split<3, RT, PT, NW>(acc, W, Wl, K, acth, actl, lda, wave, lane, bias); break;
+        case 4: if constexpr (RT >= 4) gemm_rows_split<4, RT, PT, NW>(acc, W, Wl, K, acth, actl, lda, wave, lane, bias); break;
+        default: break;
+    }
+    if (sth.active) sth.flush(acth);
+    if (stl.active) stl.flush(actl);
+}
+
+// relu_epilogue of the split recipe: relu(z) split into both planes, the same mask record.
+template <int RT, int PT, int NW = 4>
+MARF_DEV void relu_epilogue_split(f32x16 (&acc)[RT][PT], u16* acth, u16* actl, int lda, int n_rt, int wave, int lane,
+                                  uint64_t* mk, int tile) {
+    static_assert(RT * PT <= 8, "a wave's ReLU mask record holds 8 accumulator tiles of 16 bits");
+    uint32_t words[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int i = 0; i < RT; ++i) {
+        const int rt = wave + NW * i;
+        if (rt >= n_rt) continue;
+        const int rbase = rt * 32 + 4 * (lane >> 5);
+#pragma unroll
+        for (int j = 0; j < PT; ++j) {
+            const int ti = i * PT + j;
+            const int px = j * 32 + (lane & 31);
+            float o[16];
+            uint32_t bits = 0;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                float v;
+                asm volatile(
+                    "v_cmp_lt_f32_e32 vcc, 0, %2\n\t"
+                    "v_cndmask_b32_e32 %0, 0, %2, vcc\n\t"
+                    "v_addc_co_u32_e32 %1, vcc, %1, %1, vcc"
+                    : "=&v"(v), "+v"(bits)
+                    : "v"(acc[i][j][r])
+                    : "vcc");
+                o[r] = v;
+            }
+            words[ti >> 1] |= bits << (16 * (1 - (ti & 1)));
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const size_t at = (size_t)px * lda + rbase + 8 * q;
+                store4_split(acth + at, actl + at, o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
+            }
+        }
+    }
+    if (mk) *mask_record(mk, tile, wave, lane, NW) = make_uint4(words[0], words[1], words[2], words[3]);
+}
+
+// mask_epilogue of the split recipe: dz = acc * relu' from the forward's record, split into both planes.
+template <int RT, int PT, int NW = 4>
+MARF_DEV void mask_epilogue_split(f32x16 (&acc)[RT][PT], u16* acth, u16* actl, int lda, int n_rt, int wave, int lane,
+                                  uint4 mw) {
+    static_assert(RT * PT <= 8, "a wave's ReLU mask record holds 8 accumulator tiles of 16 bits");
+    const uint32_t words[4] = {mw.x, mw.y, mw.z, mw.w};
+#pragma unroll
+    for (int i = 0; i < RT; ++i) {
+        const int rt = wave + NW * i;
+        if (rt >= n_rt) continue;
+        const int rbase = rt * 32 + 4 * (lane >> 5);
+#pragma unroll
+        for (int j = 0; j < PT; ++j) {
+            const int ti = i * PT + j;
+            const int px = j * 32 + (lane & 31);
+            const uint32_t w = words[ti >> 1];
+            float o[16];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int m = __builtin_amdgcn_sbfe((int)w, 16 * (1 - (ti & 1)) + 15 - r, 1);
+                o[r] = __int_as_float(__float_as_int(acc[i][j][r]) & m);
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const size_t at = (size_t)px * lda + rbase + 8 * q;
+                store4_split(acth + at, actl + at, o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
+            }
+        }
+    }
+}
+
 }  // namespace marf

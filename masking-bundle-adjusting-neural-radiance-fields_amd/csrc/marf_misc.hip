@@ -181,6 +181,43 @@ __global__ void k_pack(const float* __restrict__ params, char* __restrict__ pack
     }
 }
 
+// MARF_BF16X3A: each matrix as two bf16 images in the bf16 pack's fragment order, hi = bf16_rne(w) then
+// lo = bf16_rne(w - float(hi)) from the fp32 remainder (Wf: hi [Mp][Kp], lo behind it; Wt likewise).
+__global__ void k_pack_split(const float* __restrict__ params, char* __restrict__ packed, PackArgs a) {
+    typedef PrecBF16 P;
+    const int l = blockIdx.y;
+    const PackLayer& L = a.ly[l];
+    u16* wf = reinterpret_cast<u16*>(packed + L.wf_off);
+    u16* wt = reinterpret_cast<u16*>(packed + L.wt_off);
+    float* bias = reinterpret_cast<float*>(packed + L.bias_off);
+    const float* W = params + L.w_off;
+    const float* bsrc = params + L.b_off;
+    const long long nf = (long long)L.Mp * L.Kp;
+    const long long nt = (long long)L.Kp * L.Mt;
+    const bool last16 = L.Mp == 16;
+    const int nkf = L.Kp / (last16 ? P::KS16 : P::KS), nkt = L.Mt / P::KS;
+    for (long long e = blockIdx.x * 256LL + threadIdx.x; e < nf + nt + L.Mp; e += (long long)gridDim.x * 256) {
+        if (e < nf) {
+            int m, k;
+            frag_coord<P>(e, nkf, last16, m, k);
+            const float wv = m < L.M && k < L.K ? W[(size_t)m * L.K + k] : 0.f;
+            const u16 hi = f2bf(wv);
+            wf[e] = hi;
+            wf[nf + e] = f2bf(wv - bf2f(hi));
+        } else if (e < nf + nt) {
+            int kr, m;
+            frag_coord<P>(e - nf, nkt, false, kr, m);
+            const float wv = m < L.M && kr < L.K ? W[(size_t)m * L.K + kr] : 0.f;
+            const u16 hi = f2bf(wv);
+            wt[e - nf] = hi;
+            wt[nt + e - nf] = f2bf(wv - bf2f(hi));
+        } else {
+            const int m = (int)(e - nf - nt);
+            bias[m] = m < L.M ? bsrc[m] : 0.f;
+        }
+    }
+}
+
 // ------------------------------------------------------------------ standalone prologue ops
 
 __global__ void k_pixel_grid(GeoDev g, float* __restrict__ xy, int n) {
@@ -381,7 +418,9 @@ hipError_t marf_launch_adam_sched(float* p, const float* g, float* m, float* v, 
 hipError_t marf_launch_pack(int dtype, const float* params, char* packed, const PackArgs& a, long long max_elems,
                             hipStream_t s) {
     dim3 grid(grid_for(max_elems), a.n_layers);
-    if (dtype == 1)
+    if (dtype == 3)
+        hipLaunchKernelGGL(k_pack_split, grid, dim3(256), 0, s, params, packed, a);
+    else if (dtype == 1)
         hipLaunchKernelGGL(k_pack<PrecBF16>, grid, dim3(256), 0, s, params, packed, a);
     else if (dtype == 2)
         hipLaunchKernelGGL(k_pack<PrecF16>, grid, dim3(256), 0, s, params, packed, a);

@@ -51,6 +51,8 @@ struct WgArgs {
     int rng_n, part0;
     int t16;           // dz / feat in the step kernel's T16 block layout (t16_off), not row-major
     WgDzlSrc dzl;      // g != null (k_wgrad_dma's DZL instantiations): dz is not read but recomputed
+    const void* dz_lo;    // k_wgrad_split: the lo planes of dz and feat (dz / feat: the hi planes)
+    const void* feat_lo;
 };
 
 template <int RT, int CT>
@@ -233,6 +235,161 @@ template <class P, int RT, int CT, int SP>
 __global__ __launch_bounds__(512, 1) void k_wgrad(WgArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     wgrad_body<P, RT, CT, SP>(a, blockIdx.x, blockIdx.y, smem);
+}
+
+// ---- MARF_BF16X3A (the mask net): both operands split into bf16 hi + lo planes,
+//   dW = dz_h^T a_h + dz_h^T a_l + dz_l^T a_h,   db = sum (dz_h + dz_l)   (fp32)
+// The register-staged body above with four LDS tiles per stage (dz hi / lo, feat hi / lo), each read
+// from HBM once; per 16-pixel k-step every accumulator tile takes 3 MFMAs from transposed-read
+// fragments.  Same [chunks][M][K] partials, so the fixed-order reduction is shared.
+template <int RT, int CT, int SP>
+MARF_DEV void wgrad_split_body(const WgArgs& a, int chunk_id, int ob, char* smem) {
+    typedef PrecBF16 P;
+    typedef u16 T;
+    constexpr int BM = WgGeo<RT, CT>::BM, BN = WgGeo<RT, CT>::BN;
+    constexpr int PADE = 32;
+    constexpr int LDZ = BM + PADE, LDF = BN + PADE;
+    constexpr int VEC = 8;
+    constexpr int NVZ = SP * BM / VEC / 512;  // vectors per thread, stage and plane
+    constexpr int NVF = SP * BN / VEC / 512;
+    static_assert(NVZ >= 1 && NVF >= 1 && SP % 16 == 0, "stage shape");
+    T* tzh = reinterpret_cast<T*>(smem);  // [SP][LDZ]
+    T* tzl = tzh + SP * LDZ;
+    T* tfh = tzl + SP * LDZ;              // [SP][LDF]
+    T* tfl = tfh + SP * LDF;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wr = wave >> 1, wc = wave & 1;
+    const int m0 = (ob / a.n_oblk_c) * BM, k0 = (ob % a.n_oblk_c) * BN;
+    const long long s_begin = (long long)chunk_id * a.chunk;
+    const long long s_end = min(s_begin + a.chunk, a.S);
+    const bool do_bias = a.bpartial && (ob % a.n_oblk_c) == 0;
+    const T* dzh = reinterpret_cast<const T*>(a.dz);
+    const T* dzl = reinterpret_cast<const T*>(a.dz_lo);
+    const T* fth = reinterpret_cast<const T*>(a.feat);
+    const T* ftl = reinterpret_cast<const T*>(a.feat_lo);
+
+    f32x16 acc[RT][CT];
+#pragma unroll
+    for (int i = 0; i < RT; ++i)
+#pragma unroll
+        for (int j = 0; j < CT; ++j) acc[i][j] = (f32x16){};
+    float bsum = 0.f;
+
+    uint4 rzh[NVZ], rzl[NVZ], rfh[NVF], rfl[NVF];
+    auto load_stage = [&](long long s0) {
+#pragma unroll
+        for (int q = 0; q < NVZ; ++q) {
+            const int e = threadIdx.x + 512 * q;
+            const int r = e / (BM / VEC), c = (e % (BM / VEC)) * VEC;
+            rzh[q] = rzl[q] = make_uint4(0, 0, 0, 0);
+            if (s0 + r < s_end && m0 + c < a.M) {
+                const size_t o = (size_t)((s0 + r) * a.ldz + m0 + c);
+                rzh[q] = *reinterpret_cast<const uint4*>(dzh + o);
+                rzl[q] = *reinterpret_cast<const uint4*>(dzl + o);
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < NVF; ++q) {
+            const int e = threadIdx.x + 512 * q;
+            const int r = e / (BN / VEC), c = (e % (BN / VEC)) * VEC;
+            rfh[q] = rfl[q] = make_uint4(0, 0, 0, 0);
+            if (s0 + r < s_end && k0 + c < a.K) {
+                const size_t o = (size_t)((s0 + r) * a.ldf + k0 + c);
+                rfh[q] = *reinterpret_cast<const uint4*>(fth + o);
+                rfl[q] = *reinterpret_cast<const uint4*>(ftl + o);
+            }
+        }
+    };
+    auto store_stage = [&]() {
+#pragma unroll
+        for (int q = 0; q < NVZ; ++q) {
+            const int e = threadIdx.x + 512 * q;
+            const int r = e / (BM / VEC), c = (e % (BM / VEC)) * VEC;
+            *reinterpret_cast<uint4*>(tzh + r * LDZ + c) = rzh[q];
+            *reinterpret_cast<uint4*>(tzl + r * LDZ + c) = rzl[q];
+        }
+#pragma unroll
+        for (int q = 0; q < NVF; ++q) {
+            const int e = threadIdx.x + 512 * q;
+            const int r = e / (BN / VEC), c = (e % (BN / VEC)) * VEC;
+            *reinterpret_cast<uint4*>(tfh + r * LDF + c) = rfh[q];
+            *reinterpret_cast<uint4*>(tfl + r * LDF + c) = rfl[q];
+        }
+    };
+    auto tr_frag = [&](const T* tile, int ld, int r0, int c0) -> P::frag {
+        const u16* base = tile + r0 * ld + c0;
+        i16x4 v[2] = {tr_read(base), tr_read(base + 4 * ld)};
+        return *reinterpret_cast<P::frag*>(v);
+    };
+
+    if (s_begin < s_end) load_stage(s_begin);
+    const int g = lane >> 4, gi = lane & 15, q4 = gi >> 2, p4 = gi & 3;
+    for (long long s0 = s_begin; s0 < s_end; s0 += SP) {
+        __syncthreads();  // previous stage fully consumed
+        store_stage();
+        __syncthreads();
+        if (s0 + SP < s_end) load_stage(s0 + SP);  // next stage in flight behind the MFMAs
+
+        if (do_bias) {
+            constexpr int RSTEP = 512 / BM > 0 ? 512 / BM : 1;
+            const int c = threadIdx.x % BM, r0 = threadIdx.x / BM;
+            if (r0 < RSTEP)
+                for (int r = r0; r < SP; r += RSTEP) bsum += bf2f(tzh[r * LDZ + c]) + bf2f(tzl[r * LDZ + c]);
+        }
+#pragma unroll
+        for (int ks = 0; ks < SP; ks += 16) {
+            const int r0 = ks + 8 * (g >> 1) + q4;  // this lane supplies row r0 (and r0 + 4)
+            P::frag zh[RT], zl[RT];
+#pragma unroll
+            for (int i = 0; i < RT; ++i) {
+                const int c0 = (wr * RT + i) * 32 + 16 * (g & 1) + 4 * p4;
+                zh[i] = tr_frag(tzh, LDZ, r0, c0);
+                zl[i] = tr_frag(tzl, LDZ, r0, c0);
+            }
+#pragma unroll
+            for (int j = 0; j < CT; ++j) {
+                const int c0 = (wc * CT + j) * 32 + 16 * (g & 1) + 4 * p4;
+                const P::frag fh = tr_frag(tfh, LDF, r0, c0), fl = tr_frag(tfl, LDF, r0, c0);
+#pragma unroll
+                for (int i = 0; i < RT; ++i) acc[i][j] = P::mma32(zh[i], fh, acc[i][j]);
+#pragma unroll
+                for (int i = 0; i < RT; ++i) acc[i][j] = P::mma32(zh[i], fl, acc[i][j]);
+#pragma unroll
+                for (int i = 0; i < RT; ++i) acc[i][j] = P::mma32(zl[i], fh, acc[i][j]);
+            }
+        }
+    }
+
+    float* out = a.partial + (size_t)chunk_id * a.M * a.K;
+#pragma unroll
+    for (int i = 0; i < RT; ++i)
+#pragma unroll
+        for (int j = 0; j < CT; ++j) {
+            const int k = k0 + (wc * CT + j) * 32 + (lane & 31);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int m = m0 + (wr * RT + i) * 32 + acc_row(lane, r);
+                if (m < a.M && k < a.K) out[(size_t)m * a.K + k] = acc[i][j][r];
+            }
+        }
+    if (do_bias) {
+        __syncthreads();
+        float* bs = reinterpret_cast<float*>(smem);
+        bs[threadIdx.x] = bsum;
+        __syncthreads();
+        constexpr int RSTEP = 512 / BM > 0 ? 512 / BM : 1;
+        if ((int)threadIdx.x < BM && m0 + (int)threadIdx.x < a.M) {
+            float s = 0.f;
+            for (int r = 0; r < RSTEP; ++r) s += bs[threadIdx.x + r * BM];
+            a.bpartial[(size_t)chunk_id * a.M + m0 + threadIdx.x] = s;
+        }
+    }
+}
+
+template <int RT, int CT, int SP>
+__global__ __launch_bounds__(512, 1) void k_wgrad_split(WgArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    wgrad_split_body<RT, CT, SP>(a, blockIdx.x, blockIdx.y, smem);
 }
 
 // ---- bf16, 256 x 256 (or 256 x 96) output blocks: LDS-DMA ring
@@ -981,6 +1138,39 @@ hipError_t marf_launch_wgrad(int dtype, const void* dz, int ldz, const void* fea
     if (cfg == 3) return launch_wg<PrecF32, 2, 2>(a, n_chunks, nr * nc, s);
     if (cfg == 1) return launch_wg<PrecF32, 2, 1>(a, n_chunks, nr * nc, s);
     return launch_wg<PrecF32, 1, 1>(a, n_chunks, nr * nc, s);
+}
+
+// 256 x 256 output blocks (2 x 4 tiles per wave), 32-pixel stages: four tiles of 32 x 288 bf16 = 72 KB.
+// The mask net's layer 0 (K = 448) takes two column blocks, the second 192 wide.
+hipError_t marf_launch_wgrad_split(const void* dz_hi, const void* dz_lo, int ldz, const void* feat_hi,
+                                   const void* feat_lo, int ldf, long long S, int M, int K, int chunk, int n_chunks,
+                                   float* partial, float* bpartial, hipStream_t s) {
+    constexpr int RT = 2, CT = 4, SP = 32;
+    constexpr int BM = WgGeo<RT, CT>::BM, BN = WgGeo<RT, CT>::BN;
+    if (!dz_hi || !dz_lo || !feat_hi || !feat_lo || ldz % 8 || ldf % 8 || chunk % SP || n_chunks < 1)
+        return hipErrorInvalidValue;
+    WgArgs a;
+    memset(&a, 0, sizeof(a));
+    a.dz = dz_hi;
+    a.dz_lo = dz_lo;
+    a.feat = feat_hi;
+    a.feat_lo = feat_lo;
+    a.S = S;
+    a.ldz = ldz;
+    a.ldf = ldf;
+    a.M = M;
+    a.K = K;
+    a.chunk = chunk;
+    a.n_chunks = n_chunks;
+    a.partial = partial;
+    a.bpartial = bpartial;
+    const int nr = (M + BM - 1) / BM, nc = (K + BN - 1) / BN;
+    a.n_oblk_c = nc;
+    const size_t lds = (size_t)SP * 2 * (BM + 32 + BN + 32) * 2;
+    hipError_t e = ensure_dynamic_lds((const void*)k_wgrad_split<RT, CT, SP>, lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_wgrad_split<RT, CT, SP>), dim3(n_chunks, nr * nc), dim3(512), lds, s, a);
+    return hipGetLastError();
 }
 
 // The range mode (WgRange) runs on the LDS-DMA kernel only: true if an M x K gradient with these

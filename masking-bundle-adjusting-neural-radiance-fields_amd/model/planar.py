@@ -9,7 +9,8 @@ Same classes, attributes, state-dict keys and training-step order as the referen
                         positional_encoding(coord_2d) (:395-471)
   ImplicitMask          mask_mapping Sequential of nn.Linear / ReLU / Sigmoid (:475-488), PosEmbedding
                         (:491-518): the learned per-pixel mask of use_implicit_mask, evaluated by
-                        Graph.predict_mask in the library's mask kernels (fp32, one process)
+                        Graph.predict_mask in the library's mask kernels (mask_precision: fp32 or
+                        bf16x3a, beside any image-net precision; one process)
 The arithmetic of the step runs in libmarf.so (marf_hip): Graph.forward is one fused HIP
 prologue+MLP kernel per tile, its backward the dgrad / warp-adjoint / weight-gradient kernels,
 the loss and Adam are HIP kernels too.  Patches shard over ranks (one process per GPU); the
@@ -75,6 +76,22 @@ def _precision(opt):
     if p in ("fp16x2", "split-fp16"):
         return marf_hip.MARF_FP16X2
     raise ValueError(f"precision must be fp32, fp16, bf16, bf16x3 or fp16x2, got {p}")
+
+
+def _mask_precision(opt):
+    """The mask network's recipe: option mask_precision (fp32 | bf16x3a), or -- unset -- the image
+    net's precision, which must then be fp32."""
+    mp = opt.get("mask_precision")
+    if mp is None:
+        return _precision(opt)
+    p = str(mp).lower()
+    if p == "fp32":
+        return marf_hip.MARF_FP32
+    if p == "bf16x3a":
+        return marf_hip.MARF_BF16X3A
+    if p in ("null", "none", ""):
+        return _precision(opt)
+    raise ValueError(f"mask_precision must be unset (null), fp32 or bf16x3a, got {mp}")
 
 
 def _dist():
@@ -518,7 +535,8 @@ class Graph(torch.nn.Module):
             if opt.get("cuda_graph"):
                 raise NotImplementedError("cuda_graph with use_implicit_mask: the captured iteration does not cover "
                                           "the mask network; turn cuda_graph off")
-            if _precision(opt) != marf_hip.MARF_FP32:
+            # the mask net's recipe is its own (mask_precision); unset, it follows `precision`
+            if _mask_precision(opt) not in (marf_hip.MARF_FP32, marf_hip.MARF_BF16X3A):
                 raise NotImplementedError(f"use_implicit_mask with precision {opt.get('precision')}: the mask "
                                           "network runs in fp32 only (plain bf16 misses the 1e-2 gradient bound, "
                                           "DESIGN.md); set precision: fp32")
@@ -582,7 +600,8 @@ class Graph(torch.nn.Module):
         if e is None:
             o = self.opt
             ph, pw = (o.patch_H, o.patch_W) if o.use_cropped_images else (o.H, o.W)
-            e = marf_hip.MaskEngine(int(o.N_vocab), _precision(o), o.H, o.W, ph, pw, crop=bool(o.use_cropped_images))
+            e = marf_hip.MaskEngine(int(o.N_vocab), _mask_precision(o), o.H, o.W, ph, pw,
+                                    crop=bool(o.use_cropped_images))
             self._mask_engines[str(device)] = e
         return e
 

@@ -1,17 +1,19 @@
 """Timing of the learned implicit mask on the GPU (no pass / fail: correctness is tested elsewhere).
 
-    python tools/bench_mask.py --part net  [--reps 20] [--out FILE]
-    python tools/bench_mask.py --part step [--reps 20] [--out FILE]
+    python tools/bench_mask.py --part net  [--reps 20] [--out FILE] [--mask-precision fp32 bf16x3a]
+    python tools/bench_mask.py --part step [--reps 20] [--out FILE] [--mask-precision fp32 bf16x3a]
 
 At the C1 size (B = 5 patches of 180 x 240 on a 360 x 480 canvas):
 
   net    forward + backward of the mask network, alternating in one process
            marf        the library's kernels (input formation + MLP + weight gradients), fp32
+           marf_bf16x3a  the same in the all-operands-split bf16 recipe (--mask-precision lists the recipes)
            stock_fp32  the same nn.Sequential through stock PyTorch on a pre-built [B*Np, 426] input
            stock_bf16  the same under torch.autocast(bfloat16)
            stock_full  stock fp32 including the input formation (embedding gather, uv features, cat)
   step   one full training iteration (forward, loss, backward, Adam) in fp32 with and without
-         use_implicit_mask, alternating
+         use_implicit_mask, and with the image net in bf16x3 beside each --mask-precision recipe of the
+         mask net (step_bf16x3_mask_fp32, step_bf16x3_mask_bf16x3a), alternating
 
 Every repetition is timed with device events after a warm-up; the JSON line gives median, min and
 max per variant, so a difference can be read against the run-to-run spread.
@@ -53,7 +55,7 @@ def timed(fns, warmup, reps):
             for k, v in ms.items()}
 
 
-def part_net(reps, warmup):
+def part_net(reps, warmup, mask_precisions=("fp32",)):
     import marf_hip
     import mask_ref
     from model.planar import ImplicitMask
@@ -63,16 +65,23 @@ def part_net(reps, warmup):
     embed = torch.randn(1500, 128, device=DEV)
     index = (torch.rand(B, 3, Np, device=DEV) < 0.1).to(torch.int32)
     dm = torch.randn(B, Np, 1, device=DEV)
-    eng = marf_hip.MaskEngine(1500, marf_hip.MARF_FP32, H, W, PH, PW)
+    codes = {"fp32": marf_hip.MARF_FP32, "bf16x3a": marf_hip.MARF_BF16X3A}
+    engs = {mp: marf_hip.MaskEngine(1500, codes[mp], H, W, PH, PW) for mp in ("fp32",) + tuple(
+        mp for mp in mask_precisions if mp != "fp32")}
+    eng = engs["fp32"]
     ps = list(net.parameters())
     xy = mask_ref.crop_grid(H, W, PH, PW).to(DEV)
     x_fixed = mask_ref.mask_input(index, embed, xy).reshape(B * Np, -1).contiguous()
     seq = net.mask_mapping
 
-    def marf():
-        for p in ps:
-            p.grad = None
-        marf_hip.mask_forward(eng, index, embed, ps).backward(dm)
+    def marf_on(e):
+        def run():
+            for p in ps:
+                p.grad = None
+            marf_hip.mask_forward(e, index, embed, ps).backward(dm)
+        return run
+
+    marf = marf_on(eng)
 
     def stock(autocast):
         def run():
@@ -88,8 +97,10 @@ def part_net(reps, warmup):
             p.grad = None
         seq(mask_ref.mask_input(index, embed, xy).reshape(B * Np, -1)).view(B, Np, 1).backward(dm)
 
-    res = timed({"marf": marf, "stock_fp32": stock(False), "stock_bf16": stock(True), "stock_full": stock_full},
-                warmup, reps)
+    fns = {"marf": marf}
+    fns.update({"marf_" + mp: marf_on(e) for mp, e in engs.items() if mp != "fp32"})
+    fns.update({"stock_fp32": stock(False), "stock_bf16": stock(True), "stock_full": stock_full})
+    res = timed(fns, warmup, reps)
     # same parameters, same input: the two fp32 paths agree (m to rounding; the gradients up to the
     # ReLU-kink flips of a random-sign upstream gradient)
     marf()
@@ -102,10 +113,19 @@ def part_net(reps, warmup):
     res["m_max_abs_diff_vs_stock_fp32"] = float((m1 - m2).abs().max())
     res["grad_cosine_vs_stock_fp32"] = float(torch.dot(g1.double(), g2.double()) / (g1.double().norm() * g2.double().norm()))
     res["grad_max_rel_diff_vs_stock_fp32"] = float((g1 - g2).abs().max() / g2.abs().max())
+    for mp, e in engs.items():
+        if mp == "fp32":
+            continue
+        marf_on(e)()
+        g3 = torch.cat([p.grad.reshape(-1) for p in ps])
+        with torch.no_grad():
+            m3 = marf_hip.mask_forward(e, index, embed, [p.detach() for p in ps])
+        res[f"m_max_abs_diff_{mp}_vs_marf_fp32"] = float((m3 - m1).abs().max())
+        res[f"grad_max_rel_diff_{mp}_vs_marf_fp32"] = float((g3 - g1).abs().max() / g1.abs().max())
     return res
 
 
-def part_step(reps, warmup):
+def part_step(reps, warmup, mask_precisions=("fp32",)):
     import options
     from model import planar
     from util import EasyDict as edict
@@ -116,11 +136,13 @@ def part_step(reps, warmup):
     rgb = torch.from_numpy(np.stack([np.roll(img, 3 * s, axis=2) for s in range(B)])).to(DEV)
     masks = torch.from_numpy((rng.random((B, 1, PH, PW)) < 0.9).astype(np.float32)).to(DEV)
     models = {}
-    for name, implicit in (("step_plain", False), ("step_implicit_mask", True)):
+    variants = [("step_plain", False, "fp32", None), ("step_implicit_mask", True, "fp32", None)]
+    variants += [(f"step_bf16x3_mask_{mp}", True, "bf16x3", mp) for mp in mask_precisions]
+    for name, implicit, prec, mp in variants:
         opt = options.override_options(options.load_options("options/planar.yaml"), edict({
-            "model": "planar", "yaml": "planar", "seed": 3, "barf_c2f": [0, 0.4], "precision": "fp32", "H": H, "W": W,
+            "model": "planar", "yaml": "planar", "seed": 3, "barf_c2f": [0, 0.4], "precision": prec, "H": H, "W": W,
             "patch_H": PH, "patch_W": PW, "batch_size": B, "max_iter": 3000, "use_edges": False,
-            "use_implicit_mask": implicit}))
+            "use_implicit_mask": implicit, "mask_precision": mp}))
         opt.device = DEV
         opt.output_path = "/tmp/marf_bench_mask"
         torch.manual_seed(3)
@@ -149,11 +171,14 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out")
+    ap.add_argument("--mask-precision", nargs="+", choices=["fp32", "bf16x3a"], default=["fp32", "bf16x3a"],
+                    help="mask-net recipes timed beside the fp32 rows")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_mask.py needs a GPU")
     res = dict(part=a.part, size=dict(B=B, H=H, W=W, patch_H=PH, patch_W=PW), device=torch.cuda.get_device_name(0))
-    res.update(part_net(a.reps, a.warmup) if a.part == "net" else part_step(a.reps, a.warmup))
+    mps = tuple(a.mask_precision)
+    res.update(part_net(a.reps, a.warmup, mps) if a.part == "net" else part_step(a.reps, a.warmup, mps))
     line = json.dumps(res)
     print(line)
     if a.out:
