@@ -46,6 +46,56 @@ typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
     } while (0)
 #endif
 
+// ------------------------------------------------------------------ aliasing-safe access
+//
+// The rule: a buffer (an LDS region, a global array) has ONE element type, the type of the pointer
+// its owner declares (u16 rows, float rows, raw char regions).  Any access to it with another type
+// -- a 16-byte vector load of a u16 row, a packed 32-bit store of two u16, a fragment read -- goes
+// through ld_as / st_as.  They access the bytes as a native integer vector marked may_alias, which
+// type-based alias analysis treats like char: it may alias every type, so the compiler never sees
+// two unrelated types on the same bytes and cannot reorder such an access across a store of the
+// home type.  The carrier has V's size and natural alignment, so the access is still one
+// full-width ds_*_b128 / global_*_dwordx4 (b64, b32); the value becomes V by __builtin_bit_cast
+// (not by a may_alias on HIP's uint4 / float4: those are class types whose copy constructor would
+// access the members with their ordinary types again).  Values in registers change type with
+// __builtin_bit_cast as well, never through a pointer.
+// (A __builtin_memcpy with __builtin_assume_aligned was tried first: the alignment assumption did
+// not survive the loop passes at the LDS bias reads of k_mlp_step, which came back 4 bytes wide.)
+template <int BYTES>
+struct AsRaw;  // the carrier of BYTES bytes
+template <>
+struct AsRaw<2> {
+    typedef u16 __attribute__((may_alias)) type;
+};
+template <>
+struct AsRaw<4> {
+    typedef uint32_t __attribute__((may_alias)) type;
+};
+template <>
+struct AsRaw<8> {
+    typedef uint32_t type __attribute__((ext_vector_type(2), may_alias));
+};
+template <>
+struct AsRaw<16> {
+    typedef uint32_t type __attribute__((ext_vector_type(4), may_alias));
+};
+template <class V>
+MARF_DEV V ld_as(const void* p) {
+    static_assert(alignof(V) == sizeof(V), "the carrier's natural alignment is V's");
+    return __builtin_bit_cast(V, *static_cast<const typename AsRaw<sizeof(V)>::type*>(p));
+}
+template <class V>
+MARF_DEV void st_as(void* p, V v) {
+    static_assert(alignof(V) == sizeof(V), "the carrier's natural alignment is V's");
+    typedef typename AsRaw<sizeof(V)>::type R;
+    *static_cast<R*>(p) = __builtin_bit_cast(R, v);
+}
+// The two 4 x 16-bit halves of a transposed LDS read as one 8-element MFMA fragment F (a, then b).
+template <class F>
+MARF_DEV F frag_of(i16x4 a, i16x4 b) {
+    return __builtin_bit_cast(F, __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
+}
+
 // ------------------------------------------------------------------ bf16 helpers
 
 MARF_DEV u16 f2bf(float x) {
@@ -97,7 +147,7 @@ struct PrecBF16 {
     static constexpr int kDtype = 1;
 
     MARF_DEV static frag load_frag(const T* p) {  // 8 contiguous bf16 (16-B aligned)
-        return *reinterpret_cast<const frag*>(p);
+        return ld_as<frag>(p);
     }
     MARF_DEV static int kofs(int lane) { return 8 * (lane >> 5); }    // 32x32 k offset
     MARF_DEV static int kofs16(int lane) { return 8 * (lane >> 4); }  // 16x16 k offset
@@ -126,7 +176,7 @@ struct PrecF16 {
     typedef f16x8 frag;
     static constexpr int kDtype = 2;
 
-    MARF_DEV static frag load_frag(const T* p) { return *reinterpret_cast<const frag*>(p); }
+    MARF_DEV static frag load_frag(const T* p) { return ld_as<frag>(p); }
     MARF_DEV static int kofs(int lane) { return 8 * (lane >> 5); }
     MARF_DEV static int kofs16(int lane) { return 8 * (lane >> 4); }
     MARF_DEV static f32x16 mma32(frag a, frag b, f32x16 c) {

@@ -24,8 +24,7 @@ MARF_DEV void copy_tile_out(const typename P::T* act, int lda, int rows, int col
         const int step = blockDim.x, dr = step / nch, dc = step - dr * nch;
         int r = threadIdx.x / nch, c = threadIdx.x - r * nch;
         for (; r < rows;) {
-            uint4 v = *reinterpret_cast<const uint4*>(act + (size_t)r * lda + 8 * c);
-            *reinterpret_cast<uint4*>(dst + (size_t)r * ldd + 8 * c) = v;
+            st_as<uint4>(dst + (size_t)r * ldd + 8 * c, ld_as<uint4>(act + (size_t)r * lda + 8 * c));
             r += dr;
             c += dc;
             if (c >= nch) {
@@ -84,11 +83,11 @@ struct TileStore {
     }
     MARF_DEV uint4 read(const T* src) const {
         constexpr int VEC = 16 / sizeof(T);
-        return *reinterpret_cast<const uint4*>(src + (size_t)row() * lda + VEC * lc);
+        return ld_as<uint4>(src + (size_t)row() * lda + VEC * lc);
     }
     MARF_DEV void write(uint4 v) {
         constexpr int VEC = 16 / sizeof(T);
-        *reinterpret_cast<uint4*>(dst + (size_t)row() * ldd + VEC * lc) = v;
+        st_as<uint4>(dst + (size_t)row() * ldd + VEC * lc, v);
         ++q;
     }
     MARF_DEV void flush(const T* src) {
@@ -240,7 +239,7 @@ MARF_DEV void gemm_tile(f32x16 (&acc)[RT][PT], const typename P::T* __restrict__
             const float* bb = bias + rt * 32 + 4 * (lane >> 5);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const float4 bv = *reinterpret_cast<const float4*>(bb + 8 * q);
+                const float4 bv = ld_as<float4>(bb + 8 * q);
                 init[4 * q] = bv.x;
                 init[4 * q + 1] = bv.y;
                 init[4 * q + 2] = bv.z;
@@ -273,13 +272,12 @@ MARF_DEV void store4(typename P::T* dst, float x0, float x1, float x2, float x3)
         uint2 v;  // one packed RNE conversion per pair
         v.x = P::pk2(x0, x1);
         v.y = P::pk2(x2, x3);
-        *reinterpret_cast<uint2*>(dst) = v;
+        st_as<uint2>(dst, v);
     } else {
-        float* d = reinterpret_cast<float*>(dst);
-        d[0] = x0;
-        d[1] = x1;
-        d[2] = x2;
-        d[3] = x3;
+        dst[0] = x0;
+        dst[1] = x1;
+        dst[2] = x2;
+        dst[3] = x3;
     }
 }
 
@@ -330,7 +328,7 @@ MARF_DEV void tile_prologue(const NetDev& net, const GeoDev& geo, int c2f_on, co
     T* row = act + (size_t)i * lda + c0;
     auto put2 = [&](int col, float a0, float a1) {  // col even
         if constexpr (sizeof(T) == 2) {
-            *reinterpret_cast<uint32_t*>(row + col) = P::pk2(a0, a1);
+            st_as<uint32_t>(row + col, P::pk2(a0, a1));
         } else {
             row[col] = a0;
             row[col + 1] = a1;
@@ -392,6 +390,7 @@ MARF_DEV void tile_prologue(const NetDev& net, const GeoDev& geo, int c2f_on, co
 // ti = i * PT + j (<= 8); tile ti's 16 bits live in word ti >> 1, bits 16 (1 - (ti & 1)) + 15 - r
 // for accumulator register r.  The dgrad epilogue of the backward finds the same (feature, pixel)
 // in the same wave / lane / register (gemm_tile deals row tiles identically for W and W^T).
+// (uint4 is these buffers' element type: every access to them is a whole record through here.)
 MARF_DEV uint4* mask_record(uint64_t* mk, int tile, int wave, int lane, int nw = 4) {
     return reinterpret_cast<uint4*>(mk) + ((size_t)tile * nw + wave) * 64 + lane;
 }
@@ -652,8 +651,8 @@ MARF_DEV void split1(float x, u16& hi, u16& lo) {
 MARF_DEV void store4_split(u16* dh, u16* dl, float x0, float x1, float x2, float x3) {
     uint2 hi, lo;
     split4(x0, x1, x2, x3, hi, lo);
-    *reinterpret_cast<uint2*>(dh) = hi;
-    *reinterpret_cast<uint2*>(dl) = lo;
+    st_as<uint2>(dh, hi);
+    st_as<uint2>(dl, lo);
 }
 
 // gemm_rows with both operands split: per k-step the A fragments hi + lo (the L2 register ring) and
@@ -677,7 +676,7 @@ MARF_DEV void gemm_rows_split(f32x16 (&acc)[RT][PT], const u16* __restrict__ Wh,
             f32x16 init;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const float4 bv = *reinterpret_cast<const float4*>(bb + 8 * q);
+                const float4 bv = ld_as<float4>(bb + 8 * q);
                 init[4 * q] = bv.x;
                 init[4 * q + 1] = bv.y;
                 init[4 * q + 2] = bv.z;

@@ -40,7 +40,7 @@ MARF_DEV void mask_prologue(const MaskFwdArgs& a, typename P::T* act, int lda, i
         if (p < g.Np) {
             int row = a.index[((size_t)b * 3 + c) * g.Np + p];
             row = row < 0 ? 0 : (row >= a.n_vocab ? a.n_vocab - 1 : row);  // never read outside the table
-            v = *reinterpret_cast<const float4*>(a.embed + (size_t)row * ED + j);
+            v = ld_as<float4>(a.embed + (size_t)row * ED + j);
         }
         store4<P>(act + (size_t)i * lda + c * ED + j, v.x, v.y, v.z, v.w);
     }
@@ -164,7 +164,7 @@ __global__ __launch_bounds__(256, 2) void k_mask_bwd(MaskBwdArgs a) {
             const float y = a.m[o];
             g = (a.dm[o] * (1.0f - y)) * y;
         }
-        *reinterpret_cast<float4*>(a.glast + (slot0 + i) * 4) = make_float4(g, 0.f, 0.f, 0.f);
+        st_as<float4>(a.glast + (slot0 + i) * 4, make_float4(g, 0.f, 0.f, 0.f));
         T* row = act + (size_t)i * lda;
         const int Kl = net.Mt[nl - 1];
         for (int c = 0; c < Kl; ++c) row[c] = P::cvt(c == 0 ? g : 0.f);
@@ -207,7 +207,7 @@ MARF_DEV void mask_prologue_split(const MaskFwdArgs& a, u16* ah, u16* al, int ld
         if (p < g.Np) {
             int row = a.index[((size_t)b * 3 + c) * g.Np + p];
             row = row < 0 ? 0 : (row >= a.n_vocab ? a.n_vocab - 1 : row);  // never read outside the table
-            v = *reinterpret_cast<const float4*>(a.embed + (size_t)row * ED + j);
+            v = ld_as<float4>(a.embed + (size_t)row * ED + j);
         }
         const size_t at = (size_t)i * lda + c * ED + j;
         store4_split(ah + at, al + at, v.x, v.y, v.z, v.w);
@@ -347,7 +347,7 @@ __global__ __launch_bounds__(256, 1) void k_mask_bwd_split(MaskBwdArgs a) {
             const float y = a.m[o];
             g = (a.dm[o] * (1.0f - y)) * y;
         }
-        *reinterpret_cast<float4*>(a.glast + (slot0 + i) * 4) = make_float4(g, 0.f, 0.f, 0.f);
+        st_as<float4>(a.glast + (slot0 + i) * 4, make_float4(g, 0.f, 0.f, 0.f));
         u16 gh, gl;
         split1(g, gh, gl);
         const size_t at = (size_t)i * lda;

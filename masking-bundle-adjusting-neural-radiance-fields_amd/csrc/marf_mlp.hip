@@ -151,7 +151,7 @@ __global__ __launch_bounds__(256, 2) void k_mlp_bwd(BwdArgs a) {
                 g[c] = (a.d_rgb[o + c] * (1.0f - y)) * y;
             }
         }
-        *reinterpret_cast<float4*>(a.glast + (slot0 + i) * 4) = make_float4(g[0], g[1], g[2], 0.f);
+        st_as<float4>(a.glast + (slot0 + i) * 4, make_float4(g[0], g[1], g[2], 0.f));
         T* row = act + (size_t)i * lda;
         const int Kl = net.Mt[nl - 1];
         for (int c = 0; c < Kl; ++c) row[c] = P::cvt(c < 3 ? g[c] : 0.f);

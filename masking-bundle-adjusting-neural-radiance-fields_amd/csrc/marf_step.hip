@@ -95,7 +95,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void k_mlp_step(StepArgs 
     __syncthreads();
     STAMP(19);
     tile_prologue<P, TP, true, NW>(net, a.geo, a.c2f.on, wsh, act, lda, b, p0);
-    if ((int)threadIdx.x < TP) *reinterpret_cast<float4*>(&gl[threadIdx.x][0]) = tg;
+    if ((int)threadIdx.x < TP) st_as<float4>(&gl[threadIdx.x][0], tg);
     __syncthreads();
     STAMP(1);
     // every saved tile streams out during the GEMM that reads it next (TileStore)
@@ -189,7 +189,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void k_mlp_step(StepArgs 
                 const int p = p0 + px;
                 float g[3] = {0.f, 0.f, 0.f};
                 float sq = 0.f, mv = 0.f;
-                const float4 tv = *reinterpret_cast<const float4*>(&gl[px][0]);  // prefetched target, mask
+                const float4 tv = ld_as<float4>(&gl[px][0]);  // prefetched target, mask
                 const float tgt[3] = {tv.x, tv.y, tv.z};
                 if (p < Np) {
                     const float m = tv.w;
@@ -207,7 +207,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void k_mlp_step(StepArgs 
                     }
                     mv = m;
                 }
-                *reinterpret_cast<float4*>(&gl[px][0]) = make_float4(g[0], g[1], g[2], 0.f);
+                st_as<float4>(&gl[px][0], make_float4(g[0], g[1], g[2], 0.f));
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {  // g = hi + lo (bf16 pair: ~16 significant bits)
                     const T hi = P::cvt(g[c]);
@@ -262,12 +262,11 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void k_mlp_step(StepArgs 
 #pragma unroll
                 for (int k0 = 0; k0 < TP; k0 += 32) {
                     typename P::frag fa;
-                    if (gi < 8) fa = *reinterpret_cast<const typename P::frag*>(&gT[gi][k0 + 8 * g]);
+                    if (gi < 8) fa = P::load_frag(&gT[gi][k0 + 8 * g]);
                     else fa = (typename P::frag){};
                     const int r0 = k0 + 8 * g + (gi >> 2);
-                    const u16* base = reinterpret_cast<const u16*>(act) + (size_t)r0 * lda + ct * 16 + 4 * (gi & 3);
-                    i16x4 v[2] = {tr_read16(base), tr_read16(base + 4 * lda)};
-                    acc = P::mma16(fa, *reinterpret_cast<typename P::frag*>(v), acc);
+                    const u16* base = act + (size_t)r0 * lda + ct * 16 + 4 * (gi & 3);
+                    acc = P::mma16(fa, frag_of<typename P::frag>(tr_read16(base), tr_read16(base + 4 * lda)), acc);
                 }
             } else {
                 const int kk = lane >> 4, n = lane & 15;

@@ -177,12 +177,14 @@ __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Ar
     const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
     float* bias_l = reinterpret_cast<float*>(smem + a.lds_bias);
     float* c2f_l = reinterpret_cast<float*>(smem + a.lds_c2f);
-    S2Layer* lyr = reinterpret_cast<S2Layer*>(smem + a.lds_layers);
+    // the per-layer table (S2Layer records) as 32-bit words: the LDS copy's one element type
+    constexpr int LYW = sizeof(S2Layer) / 4;
+    uint32_t* lyr = reinterpret_cast<uint32_t*>(smem + a.lds_layers);
     auto ly_int = [&](int l, int field) -> int {
-        return __builtin_amdgcn_readfirstlane(reinterpret_cast<const int*>(lyr + l)[field]);
+        return __builtin_amdgcn_readfirstlane((int)lyr[l * LYW + field]);
     };
     auto ly_ptr = [&](int l, int which) -> u16* {  // which 0: feat, 1: dz
-        const uint32_t* q = reinterpret_cast<const uint32_t*>(lyr + l) + 6 + 2 * which;
+        const uint32_t* q = lyr + l * LYW + 6 + 2 * which;
         const uint64_t lo = (uint32_t)__builtin_amdgcn_readfirstlane(q[0]);
         const uint64_t hi = (uint32_t)__builtin_amdgcn_readfirstlane(q[1]);
         return reinterpret_cast<u16*>(lo | (hi << 32));
@@ -200,19 +202,18 @@ __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Ar
     // ---- constants into LDS (plain loads: the compiler's waits are harmless before the ring)
     for (int e = threadIdx.x; e < a.nbias; e += NW * 64) bias_l[e] = a.bias[e];
     if ((int)threadIdx.x < 32) c2f_l[threadIdx.x] = (int)threadIdx.x < L ? a.c2f_w[threadIdx.x] : 0.f;
-    for (int e = threadIdx.x; e < nl * (int)(sizeof(S2Layer) / 4); e += NW * 64)
-        reinterpret_cast<uint32_t*>(lyr)[e] = reinterpret_cast<const uint32_t*>(a.layers)[e];
-    for (int e = lane; e < 512; e += 64) reinterpret_cast<uint32_t*>(gts)[e] = 0u;
+    for (int e = threadIdx.x; e < nl * LYW; e += NW * 64)
+        lyr[e] = ld_as<uint32_t>(reinterpret_cast<const char*>(a.layers) + 4 * e);
+    for (int e = lane; e < 512; e += 64) st_as<uint32_t>(gts + 2 * e, 0u);
     for (int e = lane; e < 3 * a.Kl; e += 64) wla[e] = 0.f;
     if constexpr (DZL_OK) {
         // the last-layer dgrad stage's row tiles (hi, then lo) for the weight gradient that recomputes
         // dz_{n-1}: the backward has no packed buffer at hand
         if (a.dzl_w && blockIdx.x == 0) {
-            const uint4* src = reinterpret_cast<const uint4*>(a.prog + (size_t)a.n_fwd * C::SLOT);
-            uint4* dst = reinterpret_cast<uint4*>(a.dzl_w);
+            const char* src = a.prog + (size_t)a.n_fwd * C::SLOT;
             for (int e = threadIdx.x; e < 2 * NRT * 64; e += NW * 64) {
                 const int part = e / (NRT * 64);
-                dst[e] = src[part * (C::LO / 16) + (e - part * NRT * 64)];
+                st_as<uint4>(a.dzl_w + 16 * (size_t)e, ld_as<uint4>(src + 16 * (size_t)(part * (C::LO / 16) + (e - part * NRT * 64))));
             }
         }
     }
@@ -364,7 +365,7 @@ __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Ar
         st_cur = 0;
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        asm volatile("" ::: "memory");  // (the stage's LDS reads stay behind the s_barrier and the DMA it publishes)
         S2T_END(0);
         S2T_BEGIN(1);
         dma_arm();
@@ -458,14 +459,14 @@ __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Ar
         constexpr int NK = decltype(nk_tag)::value;
         typedef std::integral_constant<int, 0> P0;
         typedef std::integral_constant<int, 1> P1;
-        const uint4* ah = reinterpret_cast<const uint4*>(slot + lane * 16);
-        const uint4* al = reinterpret_cast<const uint4*>(slot + C::LO + lane * 16);
+        const char* ah = slot + lane * 16;  // fragment u of the stage: 1 KB apart
+        const char* al = slot + C::LO + lane * 16;
         constexpr int P = NK < 4 ? NK : 4;
         uint4 A0[4], A1[4];
 #pragma unroll
         for (int u = 0; u < P; ++u) {
-            A0[u] = ah[u * 64];
-            if constexpr (MODE != 0) A1[u] = al[u * 64];
+            A0[u] = ld_as<uint4>(ah + u * 1024);
+            if constexpr (MODE != 0) A1[u] = ld_as<uint4>(al + u * 1024);
         }
         s2_sfor<NK>([&](auto ksc) {
             constexpr int ks = decltype(ksc)::value;
@@ -480,20 +481,20 @@ __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Ar
                     hook(ksc, P0());
                     hook(ksc, P1());
                 }
-                if constexpr (refill) A0[u] = ah[(ks + P) * 64];
+                if constexpr (refill) A0[u] = ld_as<uint4>(ah + (ks + P) * 1024);
                 if (live) piece();
             } else if constexpr (MODE == 2) {
                 if (live) {
                     mf(acc, A0[u], Bhi[ks]);
                     hook(ksc, P0());
                 }
-                if constexpr (refill) A0[u] = ah[(ks + P) * 64];
+                if constexpr (refill) A0[u] = ld_as<uint4>(ah + (ks + P) * 1024);
                 __builtin_amdgcn_sched_barrier(0);
                 if (live) {
                     mf(acc, A1[u], Bhi[ks]);
                     hook(ksc, P1());
                 }
-                if constexpr (refill) A1[u] = al[(ks + P) * 64];
+                if constexpr (refill) A1[u] = ld_as<uint4>(al + (ks + P) * 1024);
                 if (live) piece();
             } else {
                 if (live) {
@@ -505,10 +506,10 @@ __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Ar
                     mf(acc, A0[u], Blo[ks]);
                     hook(ksc, P1());
                 }
-                if constexpr (refill) A0[u] = ah[(ks + P) * 64];
+                if constexpr (refill) A0[u] = ld_as<uint4>(ah + (ks + P) * 1024);
                 __builtin_amdgcn_sched_barrier(0);
                 if (live) mf(acc, A1[u], Bhi[ks]);
-                if constexpr (refill) A1[u] = al[(ks + P) * 64];
+                if constexpr (refill) A1[u] = ld_as<uint4>(al + (ks + P) * 1024);
                 if (live) piece();
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -530,7 +531,7 @@ __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Ar
         const float* bb = bias_l + boff + rt * 32 + 4 * h;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const float4 v = *reinterpret_cast<const float4*>(bb + 8 * q);
+            const float4 v = ld_as<float4>(bb + 8 * q);
             acc[4 * q] = v.x;
             acc[4 * q + 1] = v.y;
             acc[4 * q + 2] = v.z;
@@ -747,14 +748,14 @@ __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Ar
             else
                 c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, av), b.f, c, 0, 0, 0);
         };
-        const uint4* ah = reinterpret_cast<const uint4*>(slot + lane * 16);
-        const uint4* al = reinterpret_cast<const uint4*>(slot + C::LO + lane * 16);
+        const char* ah = slot + lane * 16;  // fragment u of the stage: 1 KB apart
+        const char* al = slot + C::LO + lane * 16;
         constexpr int P = NK < 4 ? NK : 4;
         uint4 A0[4], A1[4];
 #pragma unroll
         for (int u = 0; u < P; ++u) {
-            A0[u] = ah[u * 64];
-            A1[u] = al[u * 64];
+            A0[u] = ld_as<uint4>(ah + u * 1024);
+            A1[u] = ld_as<uint4>(al + u * 1024);
         }
         s2_sfor<NK>([&](auto ksc) {
             constexpr int ks = decltype(ksc)::value;
@@ -766,14 +767,14 @@ __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Ar
             __builtin_amdgcn_sched_barrier(0);
             mma(c1, A0[u], B1[ks]);
             hook(ksc, P1());
-            if constexpr (refill) A0[u] = ah[(ks + P) * 64];
+            if constexpr (refill) A0[u] = ld_as<uint4>(ah + (ks + P) * 1024);
             __builtin_amdgcn_sched_barrier(0);
             mma(c0, A1[u], B0[ks]);
             hook(ksc, P2());
             __builtin_amdgcn_sched_barrier(0);
             mma(c1, A1[u], B1[ks]);
             hook(ksc, P3());
-            if constexpr (refill) A1[u] = al[(ks + P) * 64];
+            if constexpr (refill) A1[u] = ld_as<uint4>(al + (ks + P) * 1024);
             piece_at(ksc, nk_tag, pieces_tag);
             __builtin_amdgcn_sched_barrier(0);
         });
@@ -910,17 +911,17 @@ __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Ar
     //      element's chain of additions is the one of a serial loop.  post: the fp16x2 recipe's 2^-10.
     auto dw_last = [&](auto f16_tag, const S2Frag* Bf, float post) {
         constexpr bool F16 = decltype(f16_tag)::value;
-        // (a compiler barrier: the u16 stores of the image and the 16-B load below do not alias under
-        //  type-based alias analysis)
-        asm volatile("" ::: "memory");
-        const uint4 ga = *reinterpret_cast<const uint4*>(gts + (lane & 15) * 32 + 8 * (lane >> 4));
+        const uint4 ga = ld_as<uint4>(gts + (lane & 15) * 32 + 8 * (lane >> 4));
         const int gq = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3;
         const u16* b0 = trs + (8 * gq + q) * 16 + (pp & 1) * 8 + 4 * (pp >> 1);
         i16x4 vv[2][2];
         f32x4 r4[NKH];
         auto round_trip = [&](auto ksc) {
             constexpr int ks = decltype(ksc)::value;
-            *reinterpret_cast<uint4*>(trs + (pxl * 2 + h) * 8) = Bf[ks].u;
+            st_as<uint4>(trs + (pxl * 2 + h) * 8, Bf[ks].u);
+            // (compiler barriers, not for aliasing: the transposing read returns what OTHER lanes
+            //  stored, and the compiler models it by this lane's address alone -- the store stays
+            //  above the reads, and the next k-step's store below them)
             asm volatile("" ::: "memory");
             vv[ks & 1][0] = s2_tr16(b0);
             vv[ks & 1][1] = s2_tr16(b0 + 4 * 16);
@@ -931,9 +932,9 @@ __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Ar
             constexpr int ks = decltype(ksc)::value;
             if constexpr (ks + 1 < NKH) round_trip(std::integral_constant<int, ks + 1>());
             if constexpr (F16)
-                r4[ks] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, ga), *reinterpret_cast<f16x8*>(vv[ks & 1]), (f32x4){}, 0, 0, 0);
+                r4[ks] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, ga), frag_of<f16x8>(vv[ks & 1][0], vv[ks & 1][1]), (f32x4){}, 0, 0, 0);
             else
-                r4[ks] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, ga), *reinterpret_cast<bf16x8*>(vv[ks & 1]), (f32x4){}, 0, 0, 0);
+                r4[ks] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, ga), frag_of<bf16x8>(vv[ks & 1][0], vv[ks & 1][1]), (f32x4){}, 0, 0, 0);
         });
         float lo[NKH][3];
 #pragma unroll
@@ -1477,16 +1478,16 @@ __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Ar
                     dw_last(BF16t(), Bh, 1.0f);
                 } else {
                     // (the generic instantiation: a run-time k-step count, one k-step at a time)
-                    const bf16x8 ga = *reinterpret_cast<const bf16x8*>(gts + (lane & 15) * 32 + 8 * (lane >> 4));
+                    const bf16x8 ga = ld_as<bf16x8>(gts + (lane & 15) * 32 + 8 * (lane >> 4));
                     const int gq = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3;
                     const int nkl = a.Kl / 16, Klw = a.Kl;
 #pragma unroll
                     for (int ks = 0; ks < NKH; ++ks) {
                         if (ks < nkl) {
-                            *reinterpret_cast<uint4*>(trs + (pxl * 2 + h) * 8) = Bh[ks].u;
+                            st_as<uint4>(trs + (pxl * 2 + h) * 8, Bh[ks].u);
                             const u16* b0 = trs + (8 * gq + q) * 16 + (pp & 1) * 8 + 4 * (pp >> 1);
-                            i16x4 vv[2] = {s2_tr16(b0), s2_tr16(b0 + 4 * 16)};
-                            const f32x4 r4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ga, *reinterpret_cast<bf16x8*>(vv), (f32x4){}, 0, 0, 0);
+                            const bf16x8 fb = frag_of<bf16x8>(s2_tr16(b0), s2_tr16(b0 + 4 * 16));
+                            const f32x4 r4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ga, fb, (f32x4){}, 0, 0, 0);
                             float lo[3];
 #pragma unroll
                             for (int c = 0; c < 3; ++c) lo[c] = __shfl_down(r4[c], 16, 64);

@@ -61,7 +61,7 @@ struct WgGeo {
     static constexpr int BN = 2 * CT * 32;
 };
 
-MARF_DEV i16x4 tr_read(const u16* p) {
+MARF_DEV i16x4 tr_read(const void* p) {  // (an address for the instruction: no typed access)
     return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) i16x4*)(p));
 }
 
@@ -120,7 +120,7 @@ MARF_DEV void wgrad_body(const WgArgs& a, int chunk_id, int ob, char* smem) {
             const int r = e / (BM / VEC), c = (e % (BM / VEC)) * VEC;
             rz[q] = make_uint4(0, 0, 0, 0);
             if (s0 + r < s_end && m0 + c < a.M)
-                rz[q] = *reinterpret_cast<const uint4*>(dz + (a.t16 ? t16_off(s0 + r, m0 + c, a.ldz) : (size_t)((s0 + r) * a.ldz + m0 + c)));
+                rz[q] = ld_as<uint4>(dz + (a.t16 ? t16_off(s0 + r, m0 + c, a.ldz) : (size_t)((s0 + r) * a.ldz + m0 + c)));
         }
 #pragma unroll
         for (int q = 0; q < NVF; ++q) {
@@ -128,7 +128,7 @@ MARF_DEV void wgrad_body(const WgArgs& a, int chunk_id, int ob, char* smem) {
             const int r = e / (BN / VEC), c = (e % (BN / VEC)) * VEC;
             rf[q] = make_uint4(0, 0, 0, 0);
             if (s0 + r < s_end && k0 + c < a.K)
-                rf[q] = *reinterpret_cast<const uint4*>(ft + (a.t16 ? t16_off(s0 + r, k0 + c, a.ldf) : (size_t)((s0 + r) * a.ldf + k0 + c)));
+                rf[q] = ld_as<uint4>(ft + (a.t16 ? t16_off(s0 + r, k0 + c, a.ldf) : (size_t)((s0 + r) * a.ldf + k0 + c)));
         }
     };
     auto store_stage = [&]() {
@@ -136,13 +136,13 @@ MARF_DEV void wgrad_body(const WgArgs& a, int chunk_id, int ob, char* smem) {
         for (int q = 0; q < NVZ; ++q) {
             const int e = threadIdx.x + 512 * q;
             const int r = e / (BM / VEC), c = (e % (BM / VEC)) * VEC;
-            *reinterpret_cast<uint4*>(tz + r * LDZ + c) = rz[q];
+            st_as<uint4>(tz + r * LDZ + c, rz[q]);
         }
 #pragma unroll
         for (int q = 0; q < NVF; ++q) {
             const int e = threadIdx.x + 512 * q;
             const int r = e / (BN / VEC), c = (e % (BN / VEC)) * VEC;
-            *reinterpret_cast<uint4*>(tf + r * LDF + c) = rf[q];
+            st_as<uint4>(tf + r * LDF + c, rf[q]);
         }
     };
 
@@ -170,18 +170,14 @@ MARF_DEV void wgrad_body(const WgArgs& a, int chunk_id, int ob, char* smem) {
 #pragma unroll
                 for (int i = 0; i < RT; ++i) {
                     const int c0 = (wr * RT + i) * 32 + 16 * (g & 1) + 4 * p4;
-                    const u16* base = reinterpret_cast<const u16*>(tz) + r0 * LDZ + c0;
-                    i16x4 lo = tr_read(base), hi = tr_read(base + 4 * LDZ);
-                    i16x4 v[2] = {lo, hi};
-                    af[i] = *reinterpret_cast<typename P::frag*>(v);
+                    const u16* base = tz + r0 * LDZ + c0;
+                    af[i] = frag_of<typename P::frag>(tr_read(base), tr_read(base + 4 * LDZ));
                 }
 #pragma unroll
                 for (int j = 0; j < CT; ++j) {
                     const int c0 = (wc * CT + j) * 32 + 16 * (g & 1) + 4 * p4;
-                    const u16* base = reinterpret_cast<const u16*>(tf) + r0 * LDF + c0;
-                    i16x4 lo = tr_read(base), hi = tr_read(base + 4 * LDF);
-                    i16x4 v[2] = {lo, hi};
-                    bf[j] = *reinterpret_cast<typename P::frag*>(v);
+                    const u16* base = tf + r0 * LDF + c0;
+                    bf[j] = frag_of<typename P::frag>(tr_read(base), tr_read(base + 4 * LDF));
                 }
 #pragma unroll
                 for (int i = 0; i < RT; ++i)
@@ -284,8 +280,8 @@ MARF_DEV void wgrad_split_body(const WgArgs& a, int chunk_id, int ob, char* smem
             rzh[q] = rzl[q] = make_uint4(0, 0, 0, 0);
             if (s0 + r < s_end && m0 + c < a.M) {
                 const size_t o = (size_t)((s0 + r) * a.ldz + m0 + c);
-                rzh[q] = *reinterpret_cast<const uint4*>(dzh + o);
-                rzl[q] = *reinterpret_cast<const uint4*>(dzl + o);
+                rzh[q] = ld_as<uint4>(dzh + o);
+                rzl[q] = ld_as<uint4>(dzl + o);
             }
         }
 #pragma unroll
@@ -295,8 +291,8 @@ MARF_DEV void wgrad_split_body(const WgArgs& a, int chunk_id, int ob, char* smem
             rfh[q] = rfl[q] = make_uint4(0, 0, 0, 0);
             if (s0 + r < s_end && k0 + c < a.K) {
                 const size_t o = (size_t)((s0 + r) * a.ldf + k0 + c);
-                rfh[q] = *reinterpret_cast<const uint4*>(fth + o);
-                rfl[q] = *reinterpret_cast<const uint4*>(ftl + o);
+                rfh[q] = ld_as<uint4>(fth + o);
+                rfl[q] = ld_as<uint4>(ftl + o);
             }
         }
     };
@@ -305,21 +301,20 @@ MARF_DEV void wgrad_split_body(const WgArgs& a, int chunk_id, int ob, char* smem
         for (int q = 0; q < NVZ; ++q) {
             const int e = threadIdx.x + 512 * q;
             const int r = e / (BM / VEC), c = (e % (BM / VEC)) * VEC;
-            *reinterpret_cast<uint4*>(tzh + r * LDZ + c) = rzh[q];
-            *reinterpret_cast<uint4*>(tzl + r * LDZ + c) = rzl[q];
+            st_as<uint4>(tzh + r * LDZ + c, rzh[q]);
+            st_as<uint4>(tzl + r * LDZ + c, rzl[q]);
         }
 #pragma unroll
         for (int q = 0; q < NVF; ++q) {
             const int e = threadIdx.x + 512 * q;
             const int r = e / (BN / VEC), c = (e % (BN / VEC)) * VEC;
-            *reinterpret_cast<uint4*>(tfh + r * LDF + c) = rfh[q];
-            *reinterpret_cast<uint4*>(tfl + r * LDF + c) = rfl[q];
+            st_as<uint4>(tfh + r * LDF + c, rfh[q]);
+            st_as<uint4>(tfl + r * LDF + c, rfl[q]);
         }
     };
     auto tr_frag = [&](const T* tile, int ld, int r0, int c0) -> P::frag {
         const u16* base = tile + r0 * ld + c0;
-        i16x4 v[2] = {tr_read(base), tr_read(base + 4 * ld)};
-        return *reinterpret_cast<P::frag*>(v);
+        return frag_of<P::frag>(tr_read(base), tr_read(base + 4 * ld));
     };
 
     if (s_begin < s_end) load_stage(s_begin);
@@ -496,8 +491,8 @@ MARF_DEV void wgrad_dma_body(const WgArgs& a, int chunk_id, int ob, char* smem) 
     uint4 dzl_whi = make_uint4(0, 0, 0, 0), dzl_wlo = make_uint4(0, 0, 0, 0);
     if constexpr (DZL) {
         if (dzl) {
-            dzl_whi = *reinterpret_cast<const uint4*>(a.dzl.w + wave * 1024 + lane * 16);
-            dzl_wlo = *reinterpret_cast<const uint4*>(a.dzl.w + DZL_W_BYTES / 2 + wave * 1024 + lane * 16);
+            dzl_whi = ld_as<uint4>(a.dzl.w + wave * 1024 + lane * 16);
+            dzl_wlo = ld_as<uint4>(a.dzl.w + DZL_W_BYTES / 2 + wave * 1024 + lane * 16);
             // (the compiler's wait for the loads: here, not at their first use inside the ring)
             asm volatile("" ::"v"(dzl_whi.x), "v"(dzl_whi.y), "v"(dzl_whi.z), "v"(dzl_whi.w), "v"(dzl_wlo.x), "v"(dzl_wlo.y),
                          "v"(dzl_wlo.z), "v"(dzl_wlo.w));
@@ -577,14 +572,14 @@ MARF_DEV void wgrad_dma_body(const WgArgs& a, int chunk_id, int ob, char* smem) 
         const int ng = a.f0.nk0 - 1;
         const int g = k0 >> 2, j = k0 & 3;
         if (g < ng) {
-            *reinterpret_cast<uint32_t*>(row + 2 * (16 * g + 8 * h + j)) = P::pk2(sn[0], sn[1]);
-            *reinterpret_cast<uint32_t*>(row + 2 * (16 * g + 8 * h + 4 + j)) = P::pk2(cs[0], cs[1]);
+            st_as<uint32_t>(row + 2 * (16 * g + 8 * h + j), P::pk2(sn[0], sn[1]));
+            st_as<uint32_t>(row + 2 * (16 * g + 8 * h + 4 + j), P::pk2(cs[0], cs[1]));
         }
         // columns 16 ng .. 95: the raw coordinates (16 ng + 8 h) and zeros, one pair per thread
         for (int c = 16 * ng + 2 * sub; c < KF; c += 32) {
             const int hc = (c - 16 * ng) >> 3;
             const float val = (c - 16 * ng) == 8 * hc && hc < 2 ? (hc ? v : u) : 0.f;
-            *reinterpret_cast<uint32_t*>(row + 2 * c) = P::pk2(val, 0.f);
+            st_as<uint32_t>(row + 2 * c, P::pk2(val, 0.f));
         }
       }
     };
@@ -623,8 +618,8 @@ MARF_DEV void wgrad_dma_body(const WgArgs& a, int chunk_id, int ob, char* smem) 
     auto dzl_mma = [&](int st) {
         const char* in = smem + DZL_SM0 + (st % (NBUF + 1)) * DZL_SLOT;
         S2Frag gB;
-        gB.u = lane < 32 ? *reinterpret_cast<const uint4*>(in + DZL_MK_SET + lane * 16) : make_uint4(0, 0, 0, 0);
-        dzl_mw = *reinterpret_cast<const uint32_t*>(in + lane * 16 + (wave >> 1) * 4);
+        gB.u = lane < 32 ? ld_as<uint4>(in + DZL_MK_SET + lane * 16) : make_uint4(0, 0, 0, 0);
+        dzl_mw = ld_as<uint32_t>(in + lane * 16 + (wave >> 1) * 4);
         dzl_c = (f32x16){};
         s2_mfma<false>(dzl_c, dzl_whi, gB);
         s2_mfma<false>(dzl_c, dzl_wlo, gB);
@@ -647,8 +642,8 @@ MARF_DEV void wgrad_dma_body(const WgArgs& a, int chunk_id, int ob, char* smem) 
         f0.u = make_uint4(hw[0], hw[1], hw[2], hw[3]);
         f1.u = make_uint4(hw[4], hw[5], hw[6], hw[7]);
         char* out = smem + (st % NBUF) * STB + t16_lds(lane & 31, 32 * wave + 8 * (lane >> 5), 16);
-        *reinterpret_cast<uint4*>(out) = s2_t16_contig(f0);
-        *reinterpret_cast<uint4*>(out + 1024) = s2_t16_contig(f1);
+        st_as<uint4>(out, s2_t16_contig(f0));
+        st_as<uint4>(out + 1024, s2_t16_contig(f1));
     };
     auto issue = [&](int st) {
         const unsigned buf = lds0 + (st % NBUF) * STB;
@@ -719,7 +714,7 @@ MARF_DEV void wgrad_dma_body(const WgArgs& a, int chunk_id, int ob, char* smem) 
         else ring_wait(ahead, std::integral_constant<int, PER_ST>());
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        asm volatile("" ::: "memory");  // (the stage's LDS reads stay behind the s_barrier, which the compiler may move memory accesses across)
         // every wave is past its reads of buffer (st - 1) % NBUF: refill it
         if (st + NBUF - 1 < n_st) issue(st + NBUF - 1);
         if constexpr (DZL) {
@@ -729,7 +724,7 @@ MARF_DEV void wgrad_dma_body(const WgArgs& a, int chunk_id, int ob, char* smem) 
                     dzl_store(0);
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                     __builtin_amdgcn_s_barrier();
-                    asm volatile("" ::: "memory");
+                    asm volatile("" ::: "memory");  // (as above: LDS reads stay behind the s_barrier)
                 }
                 // stage st + 1's tile: its inputs arrived with stage st, its slot's last readers
                 // (stage st + 1 - NBUF) are behind this iteration's barrier
@@ -747,7 +742,7 @@ MARF_DEV void wgrad_dma_body(const WgArgs& a, int chunk_id, int ob, char* smem) 
 #pragma unroll
             for (int r = 0; r < SP; r += 2) {
                 const int rr = r + (threadIdx.x >> 8);
-                bsum += P::tof(*reinterpret_cast<const u16*>(tz + (T16 ? t16_lds(rr, c, 16) : swz(rr, c))));
+                bsum += P::tof(ld_as<u16>(tz + (T16 ? t16_lds(rr, c, 16) : swz(rr, c))));
             }
         }
 #pragma unroll
@@ -757,20 +752,18 @@ MARF_DEV void wgrad_dma_body(const WgArgs& a, int chunk_id, int ob, char* smem) 
 #pragma unroll
             for (int i = 0; i < RT; ++i) {
                 const int c = (wr * RT + i) * 32 + 16 * (g & 1) + 4 * p4;
-                const u16* base = reinterpret_cast<const u16*>(tz + (T16 ? t16_lds(r0, c, 16) : swz(r0, c)));
-                const u16* base4 = T16 ? reinterpret_cast<const u16*>(tz + t16_lds(r0 + 4, c, 16)) : base + 4 * 256;
-                i16x4 v[2] = {tr_read(base), tr_read(base4)};
-                af[i] = *reinterpret_cast<typename P::frag*>(v);
+                const char* base = tz + (T16 ? t16_lds(r0, c, 16) : swz(r0, c));
+                const char* base4 = T16 ? tz + t16_lds(r0 + 4, c, 16) : base + 4 * 512;
+                af[i] = frag_of<typename P::frag>(tr_read(base), tr_read(base4));
             }
 #pragma unroll
             for (int j = 0; j < CT; ++j) {
                 const int c = (wc * CT + j) * 32 + 16 * (g & 1) + 4 * p4;
                 // (F0: the recomputed feat_0 keeps its own row layout)
                 constexpr bool FT = T16 && !F0;
-                const u16* base = reinterpret_cast<const u16*>(tf + (FT ? t16_lds(r0, c, KF >> 4) : foff<KF>(r0, c)));
-                const u16* base4 = FT ? reinterpret_cast<const u16*>(tf + t16_lds(r0 + 4, c, KF >> 4)) : base + 4 * KF;
-                i16x4 v[2] = {tr_read(base), tr_read(base4)};
-                bf[j] = *reinterpret_cast<typename P::frag*>(v);
+                const char* base = tf + (FT ? t16_lds(r0, c, KF >> 4) : foff<KF>(r0, c));
+                const char* base4 = FT ? tf + t16_lds(r0 + 4, c, KF >> 4) : base + 4 * KF * 2;
+                bf[j] = frag_of<typename P::frag>(tr_read(base), tr_read(base4));
             }
 #pragma unroll
             for (int i = 0; i < RT; ++i)
@@ -832,6 +825,9 @@ __global__ __launch_bounds__(256) void k_wgrad_last(const float* __restrict__ gl
                                                     int ldf, int K, int chunk, float* partial, float* bpartial) {
     typedef typename P::T T;
     constexpr int VEC = 16 / sizeof(T);
+    struct alignas(16) Row16 {  // VEC consecutive features: one 16-byte load
+        T e[VEC];
+    };
     __shared__ float red[3072];
     __shared__ float redb[256][3];
     const T* feat = reinterpret_cast<const T*>(feat_v);
@@ -850,12 +846,11 @@ __global__ __launch_bounds__(256) void k_wgrad_last(const float* __restrict__ gl
         long long s = s_begin + pl;
 #pragma unroll 4
         for (; s < s_end; s += lanes) {
-            const float4 g = *reinterpret_cast<const float4*>(glast + s * 4);
-            const uint4 raw = *reinterpret_cast<const uint4*>(feat + s * ldf + fg * VEC);
-            const T* f = reinterpret_cast<const T*>(&raw);
+            const float4 g = ld_as<float4>(glast + s * 4);
+            const Row16 f = ld_as<Row16>(feat + s * ldf + fg * VEC);
 #pragma unroll
             for (int v = 0; v < VEC; ++v) {
-                const float x = P::tof(f[v]);
+                const float x = P::tof(f.e[v]);
                 acc[v][0] += g.x * x;
                 acc[v][1] += g.y * x;
                 acc[v][2] += g.z * x;

@@ -7,6 +7,10 @@ library computed.  The cases are the smallest shapes that reach each body of the
 MARF_STEP2_GRID (read at every launch) caps the persistent grid, so a few blocks take many tiles --
 the last-layer weight gradient accumulates over them in LDS, groups of two tiles and a last single
 tile both occur, and the dgrad runs with a sink set.
+
+The tile-* cases pin the tile kernels (plain bf16, fp32, fp16, one skip net) in the same way; their
+digests come from a build of the commit named under "tile_cases" in the fixture.  No candidate case
+had to be left out: the parent library reproduced every one in three separate processes.
 """
 import hashlib
 import os
@@ -38,6 +42,14 @@ CASES = {
     "dz": (1, 64, 64, 16, FULL, {"MARF_STEP2_GRID": "3", "MARF_STEP2_DZ": "1"}, {}),
     # k_step2h
     "fp16x2": (1, 64, 64, 16, FULL, {"MARF_STEP2_GRID": "3"}, {"precision": "fp16x2"}),
+    # the tile kernels (k_mlp_step, the k_wgrad family, marf_gemm.h), grid unconstrained: one block
+    # per 64- or 128-pixel tile.  Their partials are reduced in a fixed order, so a step's bits are a
+    # function of the build alone; each case was kept because the parent library reproduced its own
+    # digests in three separate processes ("skip": opt.arch.skip, the SK instantiation).
+    "tile-bf16": (1, 64, 64, 16, FULL, {}, {"precision": "bf16"}),
+    "tile-fp32": (1, 64, 64, 8, FULL, {}, {"precision": "fp32"}),
+    "tile-fp16": (1, 64, 64, 16, FULL, {}, {"precision": "fp16"}),
+    "tile-skip": (1, 64, 64, 8, FULL, {}, {"precision": "bf16", "skip": [2]}),
 }
 
 
@@ -49,8 +61,10 @@ def build(case, setenv, out="/tmp/marf_sched"):
     B, ph, pw, L, hidden, env, over = CASES[case]
     for k, v in env.items():
         setenv(k, v)
+    over = dict(over)
+    skip = over.pop("skip", [])
     opt = step_bits._opt(out, H=512, W=512, patch_H=ph, patch_W=pw, batch_size=B, use_edges=False,
-                         arch={"layers": [None] + list(hidden) + [3], "skip": [], "posenc": {"L_2D": L}}, **over)
+                         arch={"layers": [None] + list(hidden) + [3], "skip": skip, "posenc": {"L_2D": L}}, **over)
     torch.manual_seed(3)
     m = planar.Model(opt)
     rng = np.random.default_rng(3)
