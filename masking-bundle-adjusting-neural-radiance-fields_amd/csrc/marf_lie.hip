@@ -177,7 +177,10 @@ MARF_DEV float one_norm(const float* A, int n) {
 
 MARF_DEV void T18_scale_square(const float* A, float* E, int n, float norm) {
     float q = norm / kTheta[5];
-    float l = ceilf(log2f(q));
+    // torch's log2 of the float quotient is correctly rounded here; the device log2f is not (within
+    // 1 ulp), and just above theta * 2^k one ulp decides whether ceil() gives k or k + 1.  log2 in
+    // double, rounded once to float, is the correctly rounded value.
+    float l = ceilf((float)log2((double)q));
     int s = l > 0.0f ? (int)l : 0;
     float As[LMAX * LMAX];
     float scale = ldexpf(1.0f, -s);
