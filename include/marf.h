@@ -38,7 +38,23 @@ extern "C" {
 #define MARF_BF16 1
 #define MARF_BF16X3 2 /* split bf16: weights and forward activations as bf16 hi + lo pairs (hi*hi + hi*lo + lo*hi
                          forward, hi + lo weights in the dgrad), bf16 dz / saved tensors; fused step and
-                         marf_render only (marf_forward / marf_backward return MARF_ERR_UNSUPPORTED) */
+                         marf_render only (marf_forward / marf_backward return MARF_ERR_UNSUPPORTED).
+                         Reach: k_step2 up to 5 layers x 256, the split tile kernel beyond, up to 512 wide
+                         (no skip layers).  The split tile kernel (k_mlp_step_split, what
+                         marf_net_step_kernel names for such a net), with split(x): hi = bf16_rne(x),
+                         lo = bf16_rne(x - float(hi)):
+                           forward  z = W_h a_h + W_h a_l + W_l a_h, fp32 accumulation
+                                    (v_mfma_f32_32x32x16_bf16), the bias as the accumulator's start;
+                                    a' = relu(z) split; the layer-0 input is the fp32 prologue's features
+                                    split; the last layer's rows in the same three terms; sigmoid, loss
+                                    partials and d rgb in fp32
+                           dgrad    da = W_h^T dz_h + W_h^T dz_l + W_l^T dz_h, dz = da * relu' split (k_step2
+                                    keeps dz single bf16: two terms); the layer-0 adjoint in fp32
+                           saved    the hi planes only -- feat_l = a_h, (dz_l)_h, bf16 rows [S][Kp_l] -- and
+                                    the ReLU records: plain bf16's bytes per pixel
+                           wgrad    the bf16 launchers on the saved hi planes: dW = dz_h^T a_h, fixed-order
+                                    split-K
+                           packed   every Wf / Wt image as hi then lo (marf_net_packed_bytes: larger) */
 
 #define MARF_FP16 3   /* fp16 MFMA (v_mfma_f32_32x32x16_f16, fp32 accumulation): weights, activations, dz and the
                          saved tensors in IEEE binary16 (11 significant bits); the bf16 rate */

@@ -73,6 +73,7 @@ struct marf_net {
     size_t packed_bytes;
     int TP, lda, Kmax;
     int sTP, sNW;  // the fused step's tile (pixel slots) and waves per block (k_mlp_step)
+    bool tsplit;   // MARF_BF16X3 on the split tile kernel (k_mlp_step_split): a net k_step2 cannot hold
     size_t lds_fwd, lds_bwd, lds_step;
     int elem;  // bytes per stored element
     unsigned diag[MARF_MAX_LAYERS];  // numerics-experiment rounding codes (MARF_DIAG_PREC; MARF_DIAG_RT builds)
@@ -98,7 +99,8 @@ static void parse_diag(marf_net* n) {
     }
 }
 
-// the split recipes: every path runs k_step2's weight program (no tile-kernel arithmetic for them)
+// the split recipes: the step and the render run k_step2's weight program, or (MARF_BF16X3 nets it
+// cannot hold) the split tile kernel; the generic forward / backward kernels have no split arithmetic
 static bool split_recipe(int dtype) { return dtype == MARF_BF16X3 || dtype == MARF_FP16X2; }
 
 static bool step2_env_enabled() {
@@ -107,6 +109,15 @@ static bool step2_env_enabled() {
 }
 
 static int device_cus();
+
+// the shapes the pixel-per-wave kernel holds (a layer's hi + lo activations live in registers)
+static bool step2_shape_ok(const marf_net* n) {
+    const int nl = n->n_layers;
+    if (n->kdt != 1 || nl < 2 || nl > 5 || n->L > 32 || n->skip) return false;  // (skip nets: the tile kernels)
+    for (int l = 0; l < nl - 1; ++l)
+        if (n->Mp[l] > 256) return false;
+    return true;
+}
 
 // Which pixel-per-wave variant (marf_step2.hip) runs this net, its weight-program shape and the
 // byte layout of the program / bias table / layer-0 column map appended to the packed buffer.
@@ -119,9 +130,7 @@ static void plan_step2_net(marf_net* n, long long pixels_hint) {
     memset(&q, 0, sizeof(q));
     q.variant = -1;
     const int nl = n->n_layers;
-    if (n->kdt != 1 || nl < 2 || nl > 5 || n->L > 32 || n->skip) return;  // (skip nets: the tile kernels)
-    for (int l = 0; l < nl - 1; ++l)
-        if (n->Mp[l] > 256) return;
+    if (!step2_shape_ok(n)) return;
     // decided once, here: the split recipe always runs this kernel; plain bf16 only on request
     // (MARF_STEP2=1 at net creation), otherwise it runs the tile kernel and needs no program
     if (!split_recipe(n->dtype) && !step2_env_enabled()) return;
@@ -467,6 +476,24 @@ int marf_net_create_skip(int n_layers, const int* dims, int L, int dtype, long l
             n->lds_step = std::max(act8, df8) + dsk8;
         }
     }
+    // MARF_BF16X3 beyond k_step2's reach (more than 5 layers, or wider than 256), no skip layers: the
+    // split tile kernel, one 4-wave block per CU on two bf16 planes [sTP][lda]; sTP = 64 above 256
+    // wide, else 128 (marf_step_split.hip).  Its saved tensors are plain bf16's (elem, the record size
+    // sNW * 1024 / sTP per slot); only the packed weight images double (hi then lo).
+    n->tsplit = dtype == MARF_BF16X3 && !n->skip && !step2_shape_ok(n);
+    if (n->tsplit) {
+        n->sTP = n->Kmax > 256 ? 64 : 128;
+        n->sNW = 4;
+        n->lds_step = std::max((size_t)2 * n->sTP * n->lda * 2, (size_t)n->sTP * (n->Kp[0] + 1) * 4);
+        // k_mlp_step_split's static __shared__: wsh, red, red9, gl, gT, lsum (+ alignment slack)
+        const size_t stat = 128 + (size_t)std::max(4 * 64, 2 * n->sTP) * 2 * 4 + 4 * 9 * 4 + (size_t)n->sTP * 16 +
+                            8 * (size_t)n->sTP * 2 + 2 * (size_t)n->sTP * 4 + 512;
+        if (n->lds_step + stat > 160 * 1024) {
+            delete n;
+            return fail(MARF_ERR_UNSUPPORTED, "net_create: split tile does not fit LDS (%zu B dynamic + %zu B static)",
+                        n->lds_step, stat);
+        }
+    }
     // the 4-wave tile kernels' static __shared__ beside the dynamic tile (k_mlp_step: wsh, red, red9,
     // gl, gT, lsum, bsh; the separate forward / backward kernels hold less): checked here, so a shape
     // whose step would fail ensure_dynamic_lds at launch is refused at creation instead
@@ -479,15 +506,16 @@ int marf_net_create_skip(int n_layers, const int* dims, int L, int dtype, long l
     }
     long long off = 0;
     size_t boff = 0;
+    const int pelem = n->tsplit ? 2 * n->elem : n->elem;  // bytes per packed weight (split: hi + lo image)
     for (int l = 0; l < n_layers; ++l) {
         n->w_off[l] = off;
         off += (long long)dims[l + 1] * n->kin[l];
         n->b_off[l] = off;
         off += dims[l + 1];
         n->wf_off[l] = (long long)boff;
-        boff += rup((long long)n->Mp[l] * n->Kp[l] * n->elem, 256);
+        boff += rup((long long)n->Mp[l] * n->Kp[l] * pelem, 256);
         n->wt_off[l] = (long long)boff;
-        boff += rup((long long)n->Kp[l] * n->Mt[l] * n->elem, 256);
+        boff += rup((long long)n->Kp[l] * n->Mt[l] * pelem, 256);
         n->bias_off[l] = (long long)boff;
         boff += rup((long long)n->Mp[l] * 4, 256);
     }
@@ -509,10 +537,11 @@ int marf_net_create_skip(int n_layers, const int* dims, int L, int dtype, long l
         return fail(MARF_ERR_UNSUPPORTED,
                     "net_create: fp16x2 needs 5 layers, every hidden layer 256 wide, 8 <= L <= 16 and no skip layers");
     }
-    if (dtype == MARF_BF16X3 && n->s2.variant < 0) {
+    if (dtype == MARF_BF16X3 && n->s2.variant < 0 && !n->tsplit) {
         delete n;
         return fail(MARF_ERR_UNSUPPORTED,
-                    "net_create: split-bf16 needs <= 5 layers, hidden widths <= 256, L <= 32 and no skip layers");
+                    "net_create: split-bf16 takes no skip layers (k_step2 up to 5 layers x 256, the split tile kernel "
+                    "beyond, up to 512 wide)");
     }
     *out = n;
     return MARF_OK;
@@ -543,6 +572,7 @@ const char* marf_net_step_kernel(const marf_net* net) {
     if (!net) return "";
     if (net->s2.variant == 3) return "k_step2h";
     if (net->s2.variant >= 0) return "k_step2";
+    if (net->tsplit) return "k_mlp_step_split";
     return "k_mlp_step";
 }
 
@@ -568,9 +598,12 @@ int marf_net_pack(const marf_net* net, const float* d_params, void* d_packed, vo
         mx = std::max(mx, (long long)p.Mp * p.Kp + (long long)p.Kp * p.Mt + p.Mp);
     }
     MarfProfScope ps("pack_weights", (hipStream_t)stream);
-    // the tile kernels' layouts (Wf / Wt / bias): every path of a split-bf16 net runs k_step2's
-    // program instead (marf_forward / marf_backward refuse it), so it packs that one only
-    if (!split_recipe(net->dtype))
+    // the tile kernels' layouts (Wf / Wt / bias): every path of a k_step2 net runs its program
+    // instead (marf_forward / marf_backward refuse the split recipes), so it packs that one only; the
+    // split tile kernel takes the tile layouts with every image as hi then lo
+    if (net->tsplit)
+        HIPCHK(marf_launch_pack(3, d_params, (char*)d_packed, a, mx, (hipStream_t)stream), "net_pack split");
+    else if (!split_recipe(net->dtype))
         HIPCHK(marf_launch_pack(net->kdt, d_params, (char*)d_packed, a, mx, (hipStream_t)stream), "net_pack");
     if (net->s2.variant >= 0) {
         const Step2NetPlan& q = net->s2;
@@ -1480,6 +1513,21 @@ size_t marf_render_workspace_bytes(const marf_net* net, const marf_geometry* geo
 int marf_render(const marf_net* net, const marf_geometry* geo, const marf_c2f* c2f, const void* d_packed, float* d_rgb,
                 void* d_ws, void* stream) {
     if (!net || !geo || !d_packed || !d_rgb) return fail(MARF_ERR_INVALID, "render: NULL argument");
+    if (net->tsplit) {  // the split tile kernel's forward-only instantiation: no workspace
+        StepArgs a;
+        memset(&a, 0, sizeof(a));
+        int rc = make_geo(geo, a.geo, MARF_TILE_PAD);
+        if (rc) return rc;
+        fill_netdev(net, d_packed, a.net);
+        a.c2f = make_c2f(c2f);
+        a.rgb = d_rgb;
+        a.S = (long long)a.geo.B * a.geo.Np_pad;
+        a.lda = net->lda;
+        MarfProfScope ps("mlp_fwd", (hipStream_t)stream);
+        HIPCHK(marf_launch_mlp_step_split(a, net->sTP, true, net->lds_step, (int)(a.S / net->sTP), (hipStream_t)stream),
+               "render split");
+        return MARF_OK;
+    }
     if (!use_step2(net)) return marf_forward(net, geo, c2f, d_packed, d_rgb, nullptr, stream);
     if (!d_ws) return fail(MARF_ERR_INVALID, "render: workspace (marf_render_workspace_bytes) missing");
     if (geo->mode == MARF_GEO_GRID || geo->mode == MARF_GEO_CANVAS) {
@@ -1543,7 +1591,10 @@ int marf_step_forward(const marf_net* net, const marf_geometry* geo, const marf_
     if (net->L > 0) HIPCHK(marf_launch_c2f_weights(a.c2f, net->L, (float*)(sv + p.c2f), s), "step_forward c2f");
     {
         MarfProfScope ps("mlp_step", s);
-        HIPCHK(marf_launch_mlp_step(a, net->kdt, net->sTP, net->sNW, net->lds_step, p.n_tiles, s), "step_forward");
+        if (net->tsplit)
+            HIPCHK(marf_launch_mlp_step_split(a, net->sTP, false, net->lds_step, p.n_tiles, s), "step_forward split");
+        else
+            HIPCHK(marf_launch_mlp_step(a, net->kdt, net->sTP, net->sNW, net->lds_step, p.n_tiles, s), "step_forward");
     }
     {
         MarfProfScope ps("loss_final", s);

@@ -251,6 +251,9 @@ hipError_t marf_launch_mask_bwd(const marf::MaskBwdArgs& a, size_t lds, int n_ti
 hipError_t marf_launch_mse_mask_bwd(const float* pred, const float* gt, const float* mask, int B, int Np,
                                     const float* stats, const float* gout, float* d_mask, hipStream_t s);
 hipError_t marf_launch_mlp_step(const marf::StepArgs& a, int dtype, int TP, int NW, size_t lds, int n_tiles, hipStream_t s);
+// the split tile step of MARF_BF16X3 nets beyond k_step2's reach (marf_step_split.hip); TP 64 or 128
+hipError_t marf_launch_mlp_step_split(const marf::StepArgs& a, int TP, bool fwd_only, size_t lds, int n_tiles,
+                                      hipStream_t s);
 hipError_t marf_launch_c2f_weights(const marf::C2fDev& c, int L, float* out, hipStream_t s,
                                    const int* csrc = nullptr, int* cdst = nullptr, int cn = 0);
 hipError_t marf_launch_loss_final(const double* part, int n, float* out, const float* denom_override, hipStream_t s);

@@ -13,6 +13,13 @@
 
 namespace marf {
 
+// Transposed LDS read (gfx950 ds_read_b64_tr_b16): per 16-lane group, a 4 x 16 block of bf16 is
+// read row-major (lane gi addresses row gi >> 2, columns 4 (gi & 3) ..) and delivered
+// column-major: lane gi receives column gi of the 4 rows.
+MARF_DEV i16x4 tr_read16(const u16* p) {
+    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) i16x4*)(p));
+}
+
 template <class P>
 MARF_DEV void copy_tile_out(const typename P::T* act, int lda, int rows, int cols, typename P::T* dst, int ldd,
                             int rmode = 0) {
@@ -516,21 +523,16 @@ MARF_DEV void dgrad_epilogue(f32x16 (&acc)[RT][PT], const NetDev& net, int l, ty
 // d(Hx) and one dH[3x3] partial per tile (fixed-order wave + block sums); for explicit coordinates
 // d coords.  `red` needs 64 NW * 2 floats, `red9` NW * 9.  smem = the act tile (reused as fp32).
 // dsk: the skip layers' posenc gradient ([TP][Kp0] fp32, added to d feat_0), or null.
-template <class P, int TP, bool GRID_ONLY = false, int NW = 4>
-MARF_DEV void warp_adjoint(const NetDev& net, const GeoDev& geo, int c2f_on, const float* wsh, char* smem, int lda,
-                           int wave, int lane, int b, int p0, float* red, float* red9, float* dH_partial,
-                           float* d_coords, TileStore<typename P::T>& st, unsigned long long* sp = nullptr,
-                           const float* dsk = nullptr) {
-    typedef typename P::T T;
-    constexpr int PT = TP / 32;
-    constexpr int RT = 8 / PT;
+// warp_adjoint_tail: everything after the layer-0 dgrad GEMM (acc = d feat_0, every wave past the
+// barrier that follows the GEMM), shared with the split tile step, which runs its own three-term
+// GEMM.  FAST: the posenc sin / cos of the 16-bit prologue (band_sincos).
+template <class P, int TP, bool GRID_ONLY, int NW, bool FAST, int RT, int PT>
+MARF_DEV void warp_adjoint_tail(const f32x16 (&acc)[RT][PT], const NetDev& net, const GeoDev& geo, int c2f_on,
+                                const float* wsh, char* smem, int wave, int lane, int b, int p0, float* red,
+                                float* red9, float* dH_partial, float* d_coords, unsigned long long* sp,
+                                const float* dsk) {
     const int L = net.L;
-    const T* act = reinterpret_cast<const T*>(smem);
-    const int R = net.Kp[0], Kk = net.Mt[0], n_rt = R / 32;
-    f32x16 acc[RT][PT];
-    gemm_tile<P, RT, PT, NW>(acc, reinterpret_cast<const T*>(net.Wt[0]), Kk, n_rt, act, lda, wave, lane, nullptr, st);
-    __syncthreads();
-    MARF_STAMP(sp, 16);
+    const int R = net.Kp[0], n_rt = R / 32;
     float* df = reinterpret_cast<float*>(smem);
     const int ldf = R + 1;
 #pragma unroll
@@ -568,7 +570,7 @@ MARF_DEV void warp_adjoint(const NetDev& net, const GeoDev& geo, int c2f_on, con
     for (int q = part; q < 2 * L; q += NPART) {
         const int c = q >= L, k = q - c * L;
         float s, co;
-        band_sincos<sizeof(T) == 2>(c ? v : u, k, s, co);
+        band_sincos<FAST>(c ? v : u, k, s, co);
         float gs = row[2 + q + c * L], gc = row[2 + q + c * L + L];
         if (c2f_on) {
             const float w = wsh[k];
@@ -626,6 +628,24 @@ MARF_DEV void warp_adjoint(const NetDev& net, const GeoDev& geo, int c2f_on, con
             dH_partial[(size_t)blockIdx.x * 9 + threadIdx.x] = s;
         }
     }
+}
+
+template <class P, int TP, bool GRID_ONLY = false, int NW = 4>
+MARF_DEV void warp_adjoint(const NetDev& net, const GeoDev& geo, int c2f_on, const float* wsh, char* smem, int lda,
+                           int wave, int lane, int b, int p0, float* red, float* red9, float* dH_partial,
+                           float* d_coords, TileStore<typename P::T>& st, unsigned long long* sp = nullptr,
+                           const float* dsk = nullptr) {
+    typedef typename P::T T;
+    constexpr int PT = TP / 32;
+    constexpr int RT = 8 / PT;
+    const T* act = reinterpret_cast<const T*>(smem);
+    f32x16 acc[RT][PT];
+    gemm_tile<P, RT, PT, NW>(acc, reinterpret_cast<const T*>(net.Wt[0]), net.Mt[0], net.Kp[0] / 32, act, lda, wave, lane,
+                             nullptr, st);
+    __syncthreads();
+    MARF_STAMP(sp, 16);
+    warp_adjoint_tail<P, TP, GRID_ONLY, NW, sizeof(T) == 2>(acc, net, geo, c2f_on, wsh, smem, wave, lane, b, p0, red, red9,
+                                                           dH_partial, d_coords, sp, dsk);
 }
 
 // ======================================================================== all-operands-split bf16

@@ -23,13 +23,6 @@
 
 namespace marf {
 
-// Transposed LDS read (gfx950 ds_read_b64_tr_b16): per 16-lane group, a 4 x 16 block of bf16 is
-// read row-major (lane gi addresses row gi >> 2, columns 4 (gi & 3) ..) and delivered
-// column-major: lane gi receives column gi of the 4 rows.
-MARF_DEV i16x4 tr_read16(const u16* p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) i16x4*)(p));
-}
-
 #define STAMP(i) MARF_STAMP(sp, i)
 
 // BL: every forward bias staged in LDS at the start (sum of the hidden widths <= MARF_STEP_NBIAS):
