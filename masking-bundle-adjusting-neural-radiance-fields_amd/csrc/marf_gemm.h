@@ -1,6 +1,15 @@
 // marf_gemm.h -- device building blocks shared by the per-tile MLP kernels (marf_mlp.hip,
-// marf_step.hip): the LDS-resident activation tile GEMM (weights = MFMA A operand streamed from
-// L2, activations = B operand read from LDS), its epilogue store and tile addressing.
+// marf_step.hip, marf_step_split.hip, marf_mask.hip): the LDS-resident activation tile GEMM
+// (weights = MFMA A operand streamed from L2, activations = B operand read from LDS), plain and
+// all-operands-split, tile addressing, and the per-tile phases.
+//
+// The rule: a phase is written once, over a view of the tile (TileView<P>: one plane of P::T;
+// SplitView<BOTH>: two u16 planes, hi then lo -- "tile views" below); a recipe is a view.  Written
+// over the views: the ReLU / dgrad epilogues, the last layer's forward, the loss tail of the fused
+// step.  (The dgrad chain's loop -- record load, gemm, barrier, epilogue, barrier, queue_save -- is
+// five lines over the view in each kernel: stamps, the skip epilogue and the save differ.)  Not
+// shared, on purpose: tile_prologue against marf_step_split.hip's tile_prologue_split
+// (different band dealing and sincos) and gemm_rows against gemm_rows_split (different pipelines).
 //
 // Orientation: Z^T[out x px] = W[out x in] . A^T[in x px]: lane = output row / 8 contiguous k for
 // the weights, lane = pixel / 8 contiguous features for the activations; the accumulator holds a
@@ -300,7 +309,7 @@ MARF_DEV void tile_origin(const GeoDev& g, int tile, int TP, int& b, int& p0, lo
 // gemm_tile), fp32 tiles (unaligned LDS rows) are copied right away (job left idle).
 template <class P, int NW = 4>
 MARF_DEV void save_tile(TileStore<typename P::T>& job, const typename P::T* act, int lda, int rows, int cols,
-                        typename P::T* dst, int nk_next, int rmode = 0) {
+                        typename P::T* dst, int rmode = 0) {
     if constexpr (sizeof(typename P::T) == 2) {
         const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
         job.init(lda, dst, cols, rows, cols, wave, lane, NW);
@@ -402,80 +411,6 @@ MARF_DEV uint4* mask_record(uint64_t* mk, int tile, int wave, int lane, int nw =
     return reinterpret_cast<uint4*>(mk) + ((size_t)tile * nw + wave) * 64 + lane;
 }
 
-// Hidden-layer epilogue: ReLU of the accumulators (bias already in them) written back to act in
-// place, and (mk != null) the ReLU mask record of this wave.  Per element: v_cmp (vcc = z > 0),
-// v_cndmask (relu), v_addc (shift the bit into the tile's mask word).
-template <class P, int RT, int PT, int NW = 4>
-MARF_DEV void relu_epilogue(f32x16 (&acc)[RT][PT], typename P::T* act, int lda, int n_rt, int wave, int lane,
-                            uint64_t* mk, int tile, unsigned diag_next = 0) {
-    static_assert(RT * PT <= 8, "a wave's ReLU mask record holds 8 accumulator tiles of 16 bits");
-    (void)diag_next;  // (the next layer's rounding code: MARF_DIAG_RT builds)
-    uint32_t words[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int i = 0; i < RT; ++i) {
-        const int rt = wave + NW * i;
-        if (rt >= n_rt) continue;
-        const int rbase = rt * 32 + 4 * (lane >> 5);
-#pragma unroll
-        for (int j = 0; j < PT; ++j) {
-            const int ti = i * PT + j;
-            const int px = j * 32 + (lane & 31);
-            float o[16];
-            uint32_t bits = 0;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                float v;
-                asm volatile(
-                    "v_cmp_lt_f32_e32 vcc, 0, %2\n\t"
-                    "v_cndmask_b32_e32 %0, 0, %2, vcc\n\t"
-                    "v_addc_co_u32_e32 %1, vcc, %1, %1, vcc"
-                    : "=&v"(v), "+v"(bits)
-                    : "v"(acc[i][j][r])
-                    : "vcc");
-                o[r] = v;
-                o[r] = MARF_DIAG_ROUND(o[r], diag_next, 2);
-            }
-            words[ti >> 1] |= bits << (16 * (1 - (ti & 1)));
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                store4<P>(act + (size_t)px * lda + rbase + 8 * q, o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
-        }
-    }
-    if (mk) *mask_record(mk, tile, wave, lane, NW) = make_uint4(words[0], words[1], words[2], words[3]);
-}
-
-// Dgrad epilogue: dz = acc * relu'(feat) with this wave's mask record `mw` (loaded before the GEMM),
-// written to act.  Per element: v_bfe_i32 (0 / -1 from the bit) and v_and.
-template <class P, int RT, int PT, int NW = 4>
-MARF_DEV void mask_epilogue(f32x16 (&acc)[RT][PT], typename P::T* act, int lda, int n_rt, int wave, int lane,
-                            uint4 mw, unsigned diag_out = 0) {
-    static_assert(RT * PT <= 8, "a wave's ReLU mask record holds 8 accumulator tiles of 16 bits");
-    (void)diag_out;  // (the rounding code of the layer whose output gradient this is: MARF_DIAG_RT)
-    const uint32_t words[4] = {mw.x, mw.y, mw.z, mw.w};
-#pragma unroll
-    for (int i = 0; i < RT; ++i) {
-        const int rt = wave + NW * i;
-        if (rt >= n_rt) continue;
-        const int rbase = rt * 32 + 4 * (lane >> 5);
-#pragma unroll
-        for (int j = 0; j < PT; ++j) {
-            const int ti = i * PT + j;
-            const int px = j * 32 + (lane & 31);
-            const uint32_t w = words[ti >> 1];
-            float o[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = __builtin_amdgcn_sbfe((int)w, 16 * (1 - (ti & 1)) + 15 - r, 1);
-                o[r] = __int_as_float(__float_as_int(acc[i][j][r]) & m);
-                o[r] = MARF_DIAG_ROUND(o[r], diag_out, 3);
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                store4<P>(act + (size_t)px * lda + rbase + 8 * q, o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
-        }
-    }
-}
-
 // Skip layer's dgrad rows past its feature input (rows rt_lo * 32 .. n_rt * 32 = the posenc block,
 // model/planar.py:440-441): no ReLU, the gradient of the posenc features, added into the fp32
 // accumulator dsk [TP][Kp0] (one (pixel, feature) per lane and register: no two lanes share one).
@@ -502,20 +437,6 @@ template <class P, int TP>
 MARF_DEV int skip_lds_off(const NetDev& net, int lda) {
     const int a = TP * lda * (int)sizeof(typename P::T), d = TP * (net.Kp[0] + 1) * 4;
     return ((a > d ? a : d) + 15) & ~15;
-}
-
-// One dgrad layer of the tile kernels: dz_l = (W_l^T dz_{l+1}) * relu'(feat_l) into act (the ReLU
-// record of feat_l), and for a skip layer the posenc rows into dsk.  acc holds the GEMM.
-template <class P, int RT, int PT, int NW = 4>
-MARF_DEV void dgrad_epilogue(f32x16 (&acc)[RT][PT], const NetDev& net, int l, typename P::T* act, int lda, int wave,
-                             int lane, uint4 mw, float* dsk) {
-    const int R = net.Kp[l];
-    if (dsk && ((net.skip >> l) & 1u)) {  // (dsk: null in kernels built without skip support)
-        mask_epilogue<P, RT, PT, NW>(acc, act, lda, net.Mp[l - 1] / 32, wave, lane, mw, net.diag[l - 1]);
-        skip_epilogue<P, RT, PT, NW>(acc, dsk, net.Kp[0], net.Mp[l - 1] / 32, R / 32, wave, lane);
-    } else {
-        mask_epilogue<P, RT, PT, NW>(acc, act, lda, R / 32, wave, lane, mw, net.diag[l - 1]);
-    }
 }
 
 // Layer-0 dgrad (d feat_0 = W_0^T dz_1, act holds dz_1) and the posenc / projective-warp adjoint
@@ -828,11 +749,146 @@ MARF_DEV void gemm_tile_split(f32x16 (&acc)[RT][PT], const u16* __restrict__ W, 
     if (stl.active) stl.flush(actl);
 }
 
-// relu_epilogue of the split recipe: relu(z) split into both planes, the same mask record.
-template <int RT, int PT, int NW = 4>
-MARF_DEV void relu_epilogue_split(f32x16 (&acc)[RT][PT], u16* acth, u16* actl, int lda, int n_rt, int wave, int lane,
-                                  uint64_t* mk, int tile) {
+// ======================================================================== tile views
+//
+// The rule of the tile kernels: a phase is written once, over a view of the LDS activation tile; a
+// recipe is a view.
+//   TileView<P>      one plane [TP][lda] of P::T (fp32, bf16, fp16)
+//   SplitView<BOTH>  the all-operands-split recipe's two u16 planes, hi then lo.  BOTH is the save
+//                    policy: false = a saved tile is its hi plane (k_mlp_step_split: plain bf16's
+//                    bytes), true = both planes, the lo one S * cols elements behind the hi one (the
+//                    mask kernels; S = all pixel slots)
+// Both offer: row (a slot's row, + column = an element: Ref), put / put4 / zero (element stores: one
+// conversion, or the split into both planes),
+// gemm (the layer GEMM into the wave's accumulators; it flushes the queued save), w16 / mma16_row
+// (one k-step of the 16-row last layer: one term, or the recipe's three), queue_save / flush /
+// clear_save over the TileStore(s), save_last_input (the tile as the last-layer weight gradient
+// reads it) and feat() (the plane the fused last-layer weight gradient reads).  Structs of pointers:
+// every member inlines, nothing is dispatched at run time.  The phase functions take a view by value:
+// taken by reference, k_mlp_step's register allocation moved (4 - 8 B more scratch in its skip
+// instantiations, profiles/tile_view/README.md); by value every kernel keeps the parent's.
+template <class P_>
+struct TileView {
+    typedef P_ P;
+    typedef typename P::T T;
+    typedef typename P::frag W16;  // the last layer's weight fragment of one k-step
+    static constexpr bool SPLIT = false;
+    T* act;
+    int lda;
+    TileStore<T> st;
+
+    MARF_DEV TileView(char* smem, int lda_, int /*TP*/) : act(reinterpret_cast<T*>(smem)), lda(lda_) { st.clear(); }
+    typedef T* Ref;  // an element of the tile: row(px) + column
+    MARF_DEV Ref row(int px) const { return act + (size_t)px * lda; }
+    MARF_DEV const T* feat() const { return act; }
+    MARF_DEV void put(Ref at, float x) const { *at = P::cvt(x); }
+    MARF_DEV void put4(Ref at, float x0, float x1, float x2, float x3) const { store4<P>(at, x0, x1, x2, x3); }
+    MARF_DEV void zero(Ref at) const { *at = P::cvt(0.f); }
+    // W: rows x K, fragment-major
+    template <int RT, int PT, int NW>
+    MARF_DEV void gemm(f32x16 (&acc)[RT][PT], const void* W, int rows, int K, const float* bias, int wave, int lane) {
+        gemm_tile<P, RT, PT, NW>(acc, reinterpret_cast<const T*>(W), K, rows / 32, act, lda, wave, lane, bias, st);
+    }
+    MARF_DEV static W16 w16(const void* W, int /*K*/, int u, int lane) {
+        return P::load_frag(reinterpret_cast<const T*>(W) + ((size_t)u * 64 + lane) * P::FE);
+    }
+    MARF_DEV f32x4 mma16_row(const W16& w, int px, int u, int lane, f32x4 acc) const {
+        return P::mma16(w, P::load_frag(act + (size_t)px * lda + u * P::KS16 + P::kofs16(lane)), acc);
+    }
+    // the tile's first `cols` columns -> rows slot0 .. of dst [S][cols]: 16-bit tiles stream out
+    // behind the next gemm, fp32 tiles are copied right away (save_tile)
+    template <int NW>
+    MARF_DEV void queue_save(void* dst, long long slot0, long long /*S*/, int rows, int cols, int rmode = 0) {
+        save_tile<P, NW>(st, act, lda, rows, cols, reinterpret_cast<T*>(dst) + slot0 * cols, rmode);
+    }
+    MARF_DEV void flush() {
+        if (st.active) st.flush(act);
+    }
+    MARF_DEV void clear_save() { st.clear(); }
+    MARF_DEV void save_last_input(void* dst, long long slot0, int rows, int cols) const {  // plain copy
+        copy_tile_out<P>(act, lda, rows, cols, reinterpret_cast<T*>(dst) + slot0 * cols, cols);
+    }
+};
+
+template <bool BOTH>
+struct SplitView {
+    typedef PrecBF16 P;
+    typedef u16 T;
+    struct W16 {
+        P::frag hi, lo;
+    };
+    static constexpr bool SPLIT = true;
+    u16 *hi, *lo;
+    int lda;
+    TileStore<u16> sth, stl;
+
+    MARF_DEV SplitView(char* smem, int lda_, int TP) : hi(reinterpret_cast<u16*>(smem)), lo(hi + (size_t)TP * lda_), lda(lda_) {
+        sth.clear();
+        stl.clear();
+    }
+    typedef size_t Ref;  // the element's offset in either plane
+    MARF_DEV Ref row(int px) const { return (size_t)px * lda; }
+    MARF_DEV const u16* feat() const { return hi; }
+    MARF_DEV void put(Ref at, float x) const { split1(x, hi[at], lo[at]); }
+    MARF_DEV void put4(Ref at, float x0, float x1, float x2, float x3) const {
+        store4_split(hi + at, lo + at, x0, x1, x2, x3);
+    }
+    MARF_DEV void zero(Ref at) const {
+        hi[at] = 0;
+        lo[at] = 0;
+    }
+    // W: the hi image of rows x K elements, the lo image right behind it
+    template <int RT, int PT, int NW>
+    MARF_DEV void gemm(f32x16 (&acc)[RT][PT], const void* W, int rows, int K, const float* bias, int wave, int lane) {
+        gemm_tile_split<RT, PT, NW>(acc, reinterpret_cast<const u16*>(W), rows, K, hi, lo, lda, wave, lane, bias, sth, stl);
+    }
+    MARF_DEV static W16 w16(const void* W, int K, int u, int lane) {  // 16 padded rows: lo image at + 16 K
+        const u16* Wh = reinterpret_cast<const u16*>(W);
+        const u16* Wl = Wh + (size_t)16 * K;
+        const size_t wo = ((size_t)u * 64 + lane) * P::FE;
+        const P::frag wh = P::load_frag(Wh + wo), wl = P::load_frag(Wl + wo);
+        return W16{wh, wl};
+    }
+    MARF_DEV f32x4 mma16_row(const W16& w, int px, int u, int lane, f32x4 acc) const {  // the same three terms
+        const size_t bo = (size_t)px * lda + u * P::KS16 + P::kofs16(lane);
+        const P::frag bh = P::load_frag(hi + bo), bl = P::load_frag(lo + bo);
+        acc = P::mma16(w.hi, bh, acc);
+        acc = P::mma16(w.hi, bl, acc);
+        return P::mma16(w.lo, bh, acc);
+    }
+    template <int NW>
+    MARF_DEV void queue_save(void* dst, long long slot0, long long S, int rows, int cols, int = 0) {
+        const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        u16* d = reinterpret_cast<u16*>(dst);
+        sth.init(lda, d + slot0 * cols, cols, rows, cols, wave, lane, NW);
+        if constexpr (BOTH) stl.init(lda, d + (S + slot0) * cols, cols, rows, cols, wave, lane, NW);
+    }
+    MARF_DEV void flush() {
+        if (sth.active) sth.flush(hi);
+        if (stl.active) stl.flush(lo);
+    }
+    MARF_DEV void clear_save() {
+        sth.clear();
+        stl.clear();
+    }
+    // fp32 [S][cols] = float(hi) + float(lo): what the fp32 last-layer weight gradient reads
+    MARF_DEV void save_last_input(void* dst, long long slot0, int rows, int cols) const {
+        float* d = reinterpret_cast<float*>(dst) + slot0 * cols;
+        for (int e = threadIdx.x; e < rows * cols; e += blockDim.x) {
+            const int r = e / cols, c = e - r * cols;
+            d[(size_t)r * cols + c] = bf2f(hi[(size_t)r * lda + c]) + bf2f(lo[(size_t)r * lda + c]);
+        }
+    }
+};
+
+// Hidden-layer epilogue: ReLU of the accumulators (bias already in them) written back to the tile in
+// place, and (mk != null) the ReLU mask record of this wave.  Per element: v_cmp (vcc = z > 0),
+// v_cndmask (relu), v_addc (shift the bit into the tile's mask word).
+template <int RT, int PT, int NW = 4, class V>
+MARF_DEV void relu_epilogue(f32x16 (&acc)[RT][PT], V v, int n_rt, int wave, int lane, uint64_t* mk, int tile,
+                            unsigned diag_next = 0) {
     static_assert(RT * PT <= 8, "a wave's ReLU mask record holds 8 accumulator tiles of 16 bits");
+    (void)diag_next;  // (the next layer's rounding code: MARF_DIAG_RT builds, plain views only)
     uint32_t words[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
     for (int i = 0; i < RT; ++i) {
@@ -847,32 +903,32 @@ MARF_DEV void relu_epilogue_split(f32x16 (&acc)[RT][PT], u16* acth, u16* actl, i
             uint32_t bits = 0;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                float v;
+                float x;
                 asm volatile(
                     "v_cmp_lt_f32_e32 vcc, 0, %2\n\t"
                     "v_cndmask_b32_e32 %0, 0, %2, vcc\n\t"
                     "v_addc_co_u32_e32 %1, vcc, %1, %1, vcc"
-                    : "=&v"(v), "+v"(bits)
+                    : "=&v"(x), "+v"(bits)
                     : "v"(acc[i][j][r])
                     : "vcc");
-                o[r] = v;
+                o[r] = x;
+                if constexpr (!V::SPLIT) o[r] = MARF_DIAG_ROUND(o[r], diag_next, 2);
             }
             words[ti >> 1] |= bits << (16 * (1 - (ti & 1)));
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const size_t at = (size_t)px * lda + rbase + 8 * q;
-                store4_split(acth + at, actl + at, o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
-            }
+            for (int q = 0; q < 4; ++q) v.put4(v.row(px) + rbase + 8 * q, o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
         }
     }
     if (mk) *mask_record(mk, tile, wave, lane, NW) = make_uint4(words[0], words[1], words[2], words[3]);
 }
 
-// mask_epilogue of the split recipe: dz = acc * relu' from the forward's record, split into both planes.
-template <int RT, int PT, int NW = 4>
-MARF_DEV void mask_epilogue_split(f32x16 (&acc)[RT][PT], u16* acth, u16* actl, int lda, int n_rt, int wave, int lane,
-                                  uint4 mw) {
+// Dgrad epilogue: dz = acc * relu'(feat) with this wave's mask record `mw` (loaded before the GEMM),
+// written to the tile.  Per element: v_bfe_i32 (0 / -1 from the bit) and v_and.
+template <int RT, int PT, int NW = 4, class V>
+MARF_DEV void mask_epilogue(f32x16 (&acc)[RT][PT], V v, int n_rt, int wave, int lane, uint4 mw,
+                            unsigned diag_out = 0) {
     static_assert(RT * PT <= 8, "a wave's ReLU mask record holds 8 accumulator tiles of 16 bits");
+    (void)diag_out;  // (the rounding code of the layer whose output gradient this is: MARF_DIAG_RT)
     const uint32_t words[4] = {mw.x, mw.y, mw.z, mw.w};
 #pragma unroll
     for (int i = 0; i < RT; ++i) {
@@ -889,12 +945,227 @@ MARF_DEV void mask_epilogue_split(f32x16 (&acc)[RT][PT], u16* acth, u16* actl, i
             for (int r = 0; r < 16; ++r) {
                 const int m = __builtin_amdgcn_sbfe((int)w, 16 * (1 - (ti & 1)) + 15 - r, 1);
                 o[r] = __int_as_float(__float_as_int(acc[i][j][r]) & m);
+                if constexpr (!V::SPLIT) o[r] = MARF_DIAG_ROUND(o[r], diag_out, 3);
             }
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const size_t at = (size_t)px * lda + rbase + 8 * q;
-                store4_split(acth + at, actl + at, o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
+            for (int q = 0; q < 4; ++q) v.put4(v.row(px) + rbase + 8 * q, o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
+        }
+    }
+}
+
+// One dgrad layer of the plain tile kernels: dz_l = (W_l^T dz_{l+1}) * relu'(feat_l) into the tile (the
+// ReLU record of feat_l), and for a skip layer the posenc rows into dsk.  acc holds the GEMM.
+template <int RT, int PT, int NW = 4, class V>
+MARF_DEV void dgrad_epilogue(f32x16 (&acc)[RT][PT], const NetDev& net, int l, V v, int wave, int lane, uint4 mw,
+                             float* dsk) {
+    const int R = net.Kp[l];
+    if (dsk && ((net.skip >> l) & 1u)) {  // (dsk: null in kernels built without skip support)
+        mask_epilogue<RT, PT, NW>(acc, v, net.Mp[l - 1] / 32, wave, lane, mw, net.diag[l - 1]);
+        skip_epilogue<typename V::P, RT, PT, NW>(acc, dsk, net.Kp[0], net.Mp[l - 1] / 32, R / 32, wave, lane);
+    } else {
+        mask_epilogue<RT, PT, NW>(acc, v, R / 32, wave, lane, mw, net.diag[l - 1]);
+    }
+}
+
+// ======================================================================== last layer, forward
+//
+// NOUT <= 3 real output rows (padded to 16) in the 16x16 MFMA form: a wave takes TP / NW pixels in
+// NJ = TP / NW / 16 groups of 16; acc[j][c] is row c of pixel wave * (TP / NW) + j * 16 + lane, held
+// in lanes 0 - 15.
+template <int TP, int NW, class V>
+MARF_DEV void last_layer_gemm(V v, const void* W, int K, int wave, int lane, f32x4 (&acc)[TP / NW / 16]) {
+    constexpr int NJ = TP / NW / 16;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[j] = (f32x4){};
+    // (the loop runs on k0 and w16 names both weight loads: counted in k-steps, with the lo image's
+    // address formed in the load, the split view's lo weight load sank behind the two hi MFMAs -- two
+    // serial L2 latencies per k-step, and the C5 step and render about 1 % and 1.6 % slower)
+    for (int k0 = 0; k0 < K; k0 += V::P::KS16) {
+        const typename V::W16 w = V::w16(W, K, k0 / V::P::KS16, lane);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+            acc[j] = v.mma16_row(w, wave * (TP / NW) + j * 16 + (lane & 15), k0 / V::P::KS16, lane, acc[j]);
+    }
+}
+
+// ... then bias and sigmoid (fp32) of the tile's real pixels to out_all[b][p][NOUT]
+template <int TP, int NW, int NOUT, class V>
+MARF_DEV void last_layer_fwd(V v, const NetDev& net, int wave, int lane, int b, int p0, int Np, float* out_all) {
+    constexpr int NJ = TP / NW / 16;
+    const int l = net.n_layers - 1;
+    f32x4 acc[NJ];
+    last_layer_gemm<TP, NW>(v, net.Wf[l], net.Kp[l], wave, lane, acc);
+    if (lane < 16) {
+        const float* bias = net.bias[l];
+        float* out = out_all + (size_t)b * Np * NOUT;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int p = p0 + wave * (TP / NW) + j * 16 + lane;
+            if (p < Np) {
+                float* o = out + (size_t)p * NOUT;
+#pragma unroll
+                for (int c = 0; c < NOUT; ++c) {
+                    const float z = acc[j][c] + bias[c];
+                    o[c] = 1.0f / (1.0f + expf(-z));
+                }
             }
+        }
+    }
+}
+
+// ======================================================================== loss tail of the fused step
+//
+// Shared by k_mlp_step and k_mlp_step_split.  gl / gT / lsum are the kernel's own __shared__ arrays,
+// taken by reference to array so every access stays an LDS access.
+
+// Target + mask of the tile's slots, loaded at the kernel's start and parked in gl until the loss
+// needs them.  Straight-line (every thread loads, padding slots a clamped valid pixel, zeroed after)
+// so the compiler counts the loads and an early barrier need not wait for them.
+template <int TP>
+MARF_DEV float4 step_target(const StepArgs& a, int b, int p0) {
+    const int Np = a.geo.Np;
+    const int ti = threadIdx.x & (TP - 1);
+    const int pc = min(p0 + ti, Np - 1);
+    const float* gb = a.gt + (size_t)b * 3 * Np + pc;
+    const float* mb = a.mask ? a.mask + (size_t)b * Np + pc : gb;
+    float4 tg = make_float4(gb[0], gb[Np], gb[2 * (size_t)Np], mb[0]);
+    if (!a.mask) tg.w = 1.0f;
+    if (p0 + ti >= Np) tg = make_float4(0.f, 0.f, 0.f, 0.f);
+    return tg;
+}
+
+// Per slot of the wave's 16-pixel groups (lanes 0 - 15; acc = last_layer_gemm's): sigmoid, rgb,
+// masked-MSE partial and d rgb, sigmoid backward -> gl (fp32), gT (channel-major, hi + lo of P::T),
+// lsum (((p-g) m)^2 and m).
+template <class P, int TP, int NW, int NJ>
+MARF_DEV void step_loss_slots(const StepArgs& a, const f32x4 (&acc)[NJ], int wave, int lane, int b, int p0,
+                              float (&gl)[TP][4], typename P::T (&gT)[8][TP], float (&lsum)[2][TP]) {
+    typedef typename P::T T;
+    const int Np = a.geo.Np;
+    if (lane < 16) {
+        const float* bl = a.net.bias[a.net.n_layers - 1];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int px = wave * (TP / NW) + j * 16 + lane;
+            const int p = p0 + px;
+            float g[3] = {0.f, 0.f, 0.f};
+            float sq = 0.f, mv = 0.f;
+            const float4 tv = ld_as<float4>(&gl[px][0]);  // prefetched target, mask
+            const float tgt[3] = {tv.x, tv.y, tv.z};
+            if (p < Np) {
+                const float m = tv.w;
+                float* o = a.rgb ? a.rgb + ((size_t)b * Np + p) * 3 : nullptr;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const float z = acc[j][c] + bl[c];
+                    const float y = 1.0f / (1.0f + expf(-z));
+                    if (o) o[c] = y;
+                    // model/planar.py:388-390 and its autograd: x = (p - g) m, d = 2 x m
+                    const float x = (y - tgt[c]) * m;
+                    sq += x * x;
+                    const float d = (2.0f * x) * m;
+                    g[c] = (d * (1.0f - y)) * y;  // torch sigmoid_backward
+                }
+                mv = m;
+            }
+            st_as<float4>(&gl[px][0], make_float4(g[0], g[1], g[2], 0.f));
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {  // g = hi + lo (bf16 pair: ~16 significant bits)
+                const T hi = P::cvt(g[c]);
+                gT[c][px] = hi;
+                gT[4 + c][px] = P::cvt(g[c] - P::tof(hi));
+            }
+            gT[3][px] = P::cvt(0.f);
+            gT[7][px] = P::cvt(0.f);
+            lsum[0][px] = sq;
+            lsum[1][px] = mv;
+        }
+    }
+}
+
+// Masked-MSE partial of the tile (fp64, fixed order; wave 0) and the last bias gradient (wave 1).
+template <int TP>
+MARF_DEV void step_tile_partials(const StepArgs& a, int wave, int lane, const float (&gl)[TP][4],
+                                 const float (&lsum)[2][TP]) {
+    if (wave == 0) {
+        double s0 = 0.0, s1 = 0.0;
+        for (int px = lane; px < TP; px += 64) {
+            s0 += (double)lsum[0][px];
+            s1 += (double)lsum[1][px];
+        }
+        s0 = wave_total63(s0);
+        s1 = wave_total63(s1);
+        if (lane == 63) {
+            a.loss_partial[2 * (size_t)blockIdx.x] = s0;
+            a.loss_partial[2 * (size_t)blockIdx.x + 1] = s1;
+        }
+    } else if (wave == 1) {
+        float s[3] = {0.f, 0.f, 0.f};
+        for (int px = lane; px < TP; px += 64)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) s[c] += gl[px][c];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float t = wave_total63(s[c]);
+            if (lane == 63) a.blast_partial[(size_t)blockIdx.x * 3 + c] = t;
+        }
+    }
+}
+
+// Last-layer weight gradient of the tile: dW[c][k] = sum_px g[px][c] feat[px][k] (feat: the tile
+// plane [TP][lda] holding feat_{n-1}; a split view's hi plane).  16x16 MFMA, A = g^T (rows 0-2: the
+// hi parts of the 3 channels, rows 4-6: lo parts), B = feat (pixels x features, transposed LDS read
+// for 16-bit T); hi + lo rows are added after the K loop.  Column tiles of 16 features dealt
+// round-robin to the waves.
+template <class P, int TP, int NW>
+MARF_DEV void step_wlast_grad(const StepArgs& a, int Kl, const typename P::T* feat, int lda, int wave, int lane,
+                              const typename P::T (&gT)[8][TP]) {
+    typedef typename P::T T;
+    float* wout = a.wlast_partial + (size_t)blockIdx.x * 3 * Kl;
+    for (int ct = wave; ct < Kl / 16; ct += NW) {
+        f32x4 acc = (f32x4){};
+        if constexpr (sizeof(T) == 2) {
+            const int g = lane >> 4, gi = lane & 15;
+#pragma unroll
+            for (int k0 = 0; k0 < TP; k0 += 32) {
+                typename P::frag fa;
+                if (gi < 8) fa = P::load_frag(&gT[gi][k0 + 8 * g]);
+                else fa = (typename P::frag){};
+                const int r0 = k0 + 8 * g + (gi >> 2);
+                const u16* base = feat + (size_t)r0 * lda + ct * 16 + 4 * (gi & 3);
+                acc = P::mma16(fa, frag_of<typename P::frag>(tr_read16(base), tr_read16(base + 4 * lda)), acc);
+            }
+        } else {
+            const int kk = lane >> 4, n = lane & 15;
+            for (int k0 = 0; k0 < TP; k0 += 4) {
+                const float fa = n < 8 ? P::tof(gT[n][k0 + kk]) : 0.f;
+                const float fb = P::tof(feat[(size_t)(k0 + kk) * lda + ct * 16 + n]);
+                acc = P::mma16(fa, fb, acc);
+            }
+        }
+        // accumulator: lane l, reg r -> row 4 (l >> 4) + r, column l & 15: hi rows in lanes
+        // 0-15, lo rows in lanes 16-31
+        float lo[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) lo[c] = __shfl_down(acc[c], 16, 64);
+        if (lane < 16) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) wout[(size_t)c * Kl + ct * 16 + lane] = acc[c] + lo[c];
+        }
+    }
+}
+
+// d (last-layer input) operand of the dgrad chain: tile columns 0 .. Kt) of every slot = g (gl), zero
+// past the 3 channels.  (A split view stores split1(g): the bits of gT's hi and lo rows.)
+template <int TP, class V>
+MARF_DEV void step_fill_d(V v, const float (&gl)[TP][4], int Kt, unsigned diag) {
+    (void)diag;  // (MARF_DIAG_RT builds, plain views only)
+    if ((int)threadIdx.x < TP) {
+        const int i = threadIdx.x;
+        for (int c = 0; c < Kt; ++c) {
+            float x = c < 3 ? gl[i][c] : 0.f;
+            if constexpr (!V::SPLIT) x = MARF_DIAG_ROUND(x, diag, 3);
+            v.put(v.row(i) + c, x);
         }
     }
 }

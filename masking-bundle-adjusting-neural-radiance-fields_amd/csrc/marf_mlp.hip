@@ -18,6 +18,10 @@
 //
 // 256 threads = 4 waves per block.  Output row tiles (32) of a layer are dealt round-robin to the
 // 4 waves; each wave covers all PT = TP/32 pixel tiles, RT*PT = 8 accumulator tiles (128 VGPRs).
+//
+// Both kernels work on a TileView<P> (marf_gemm.h: a phase is written once over a tile view, a recipe
+// is a view): the epilogues and the last layer's forward (last_layer_fwd) are shared with the step,
+// split-step and mask kernels.
 #include "marf_gemm.h"
 
 namespace marf {
@@ -28,15 +32,13 @@ namespace marf {
 // nets registers and spills)
 template <class P, int TP, bool SK>
 __global__ __launch_bounds__(256, 2) void k_mlp_fwd(FwdArgs a) {
-    typedef typename P::T T;
     constexpr int PT = TP / 32;
     constexpr int RT = 8 / PT;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    T* act = reinterpret_cast<T*>(smem);
     __shared__ float wsh[32];
 
     const NetDev& net = a.net;
-    const int lda = a.lda;
+    TileView<P> v(smem, a.lda, TP);
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     int b, p0;
     long long slot0;
@@ -44,88 +46,50 @@ __global__ __launch_bounds__(256, 2) void k_mlp_fwd(FwdArgs a) {
 
     c2f_weights_lds(a.c2f, net.L, wsh);
     __syncthreads();
-    tile_prologue<P, TP>(net, a.geo, a.c2f.on, wsh, act, lda, b, p0);
+    tile_prologue<P, TP>(net, a.geo, a.c2f.on, wsh, v.act, v.lda, b, p0);
     __syncthreads();
-    TileStore<T> st;
-    st.clear();
-    if (a.feat[0])
-        save_tile<P>(st, act, lda, TP, net.Kp[0], reinterpret_cast<T*>(a.feat[0]) + slot0 * net.Kp[0], net.Kp[0] / P::KS);
+    if (a.feat[0]) v.template queue_save<4>(a.feat[0], slot0, 0, TP, net.Kp[0]);
 
     // ---- hidden layers
     const int nl = net.n_layers;
     for (int l = 0; l < nl - 1; ++l) {
-        const int K = net.Kp[l], M = net.Mp[l], n_rt = M / 32;
+        const int K = net.Kp[l], M = net.Mp[l];
         f32x16 acc[RT][PT];
-        gemm_tile<P, RT, PT>(acc, reinterpret_cast<const T*>(net.Wf[l]), K, n_rt, act, lda, wave, lane, net.bias[l], st);
+        v.template gemm<RT, PT, 4>(acc, net.Wf[l], M, K, net.bias[l], wave, lane);
         __syncthreads();  // every wave has consumed the layer input
-        relu_epilogue<P, RT, PT>(acc, act, lda, n_rt, wave, lane, a.mask[l + 1], blockIdx.x, net.diag[l + 1]);
+        relu_epilogue<RT, PT>(acc, v, M / 32, wave, lane, a.mask[l + 1], blockIdx.x, net.diag[l + 1]);
         __syncthreads();
         if (SK && ((net.skip >> (l + 1)) & 1u)) {  // skip layer: [feature ; posenc] (model/planar.py:440-441)
-            tile_prologue<P, TP>(net, a.geo, a.c2f.on, wsh, act, lda, b, p0, M);
+            tile_prologue<P, TP>(net, a.geo, a.c2f.on, wsh, v.act, v.lda, b, p0, M);
             __syncthreads();
         }
-        st.clear();
+        v.clear_save();
         if (a.feat[l + 1]) {
             const int Kn = net.Kp[l + 1];  // (M + Kp0 for a skip layer)
             if (l + 1 < nl - 1)
-                save_tile<P>(st, act, lda, TP, Kn, reinterpret_cast<T*>(a.feat[l + 1]) + slot0 * Kn, Kn / P::KS);
+                v.template queue_save<4>(a.feat[l + 1], slot0, 0, TP, Kn);
             else  // input of the last (16x16) layer: plain copy
-                copy_tile_out<P>(act, lda, TP, M, reinterpret_cast<T*>(a.feat[l + 1]) + slot0 * M, M);
+                v.save_last_input(a.feat[l + 1], slot0, TP, M);
         }
     }
 
     // ---- last layer (3 outputs, rows padded to 16): 16x16 MFMA, TP/4 pixels per wave, sigmoid
-    {
-        const int l = nl - 1;
-        const int K = net.Kp[l];
-        const T* W = reinterpret_cast<const T*>(net.Wf[l]);
-        constexpr int NJ = TP / 64;
-        f32x4 acc[NJ];
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) acc[j] = (f32x4){};
-        const int ko = P::kofs16(lane);
-        for (int k0 = 0; k0 < K; k0 += P::KS16) {
-            typename P::frag wa = P::load_frag(W + ((size_t)(k0 / P::KS16) * 64 + lane) * P::FE);
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                const int px = wave * (TP / 4) + j * 16 + (lane & 15);
-                typename P::frag bb = P::load_frag(act + (size_t)px * lda + k0 + ko);
-                acc[j] = P::mma16(wa, bb, acc[j]);
-            }
-        }
-        if (lane < 16) {
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                const int px = wave * (TP / 4) + j * 16 + lane;
-                const int p = p0 + px;
-                if (p < a.geo.Np) {
-                    float* o = a.rgb + ((size_t)b * a.geo.Np + p) * 3;
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        float z = acc[j][c] + net.bias[l][c];
-                        o[c] = 1.0f / (1.0f + expf(-z));
-                    }
-                }
-            }
-        }
-    }
+    last_layer_fwd<TP, 4, 3>(v, net, wave, lane, b, p0, a.geo.Np, a.rgb);
 }
 
 // ======================================================================== backward
 
 template <class P, int TP>
 __global__ __launch_bounds__(256, 2) void k_mlp_bwd(BwdArgs a) {
-    typedef typename P::T T;
     constexpr int PT = TP / 32;
     constexpr int RT = 8 / PT;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    T* act = reinterpret_cast<T*>(smem);
     __shared__ float wsh[32];
     __shared__ float red[4 * TP * 2];
     __shared__ float red9[4 * 9];
 
     const NetDev& net = a.net;
-    const int lda = a.lda;
+    TileView<P> v(smem, a.lda, TP);
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     int b, p0;
     long long slot0;
@@ -135,7 +99,7 @@ __global__ __launch_bounds__(256, 2) void k_mlp_bwd(BwdArgs a) {
     c2f_weights_lds(a.c2f, net.L, wsh);
     float* dsk = nullptr;  // skip nets: the posenc gradient of the skip layers
     if (net.skip) {
-        dsk = reinterpret_cast<float*>(smem + skip_lds_off<P, TP>(net, lda));
+        dsk = reinterpret_cast<float*>(smem + skip_lds_off<P, TP>(net, v.lda));
         for (int e = threadIdx.x; e < TP * net.Kp[0]; e += 256) dsk[e] = 0.f;
     }
 
@@ -152,28 +116,25 @@ __global__ __launch_bounds__(256, 2) void k_mlp_bwd(BwdArgs a) {
             }
         }
         st_as<float4>(a.glast + (slot0 + i) * 4, make_float4(g[0], g[1], g[2], 0.f));
-        T* row = act + (size_t)i * lda;
         const int Kl = net.Mt[nl - 1];
-        for (int c = 0; c < Kl; ++c) row[c] = P::cvt(c < 3 ? g[c] : 0.f);
+        for (int c = 0; c < Kl; ++c) v.put(v.row(i) + c, c < 3 ? g[c] : 0.f);
     }
     __syncthreads();
 
     // ---- dgrad chain, l = nl-1 .. 1 : dfeat_l = W_l^T dz_{l+1}; dz_l = dfeat_l * relu'(feat_l)
-    TileStore<T> st;
-    st.clear();
     for (int l = nl - 1; l >= 1; --l) {
-        const int R = net.Kp[l], Kk = net.Mt[l], n_rt = R / 32;
+        const int R = net.Kp[l], Kk = net.Mt[l];
         f32x16 acc[RT][PT];
         const uint4 mw = *mask_record(const_cast<uint64_t*>(a.mask[l]), blockIdx.x, wave, lane);
-        gemm_tile<P, RT, PT>(acc, reinterpret_cast<const T*>(net.Wt[l]), Kk, n_rt, act, lda, wave, lane, nullptr, st);
+        v.template gemm<RT, PT, 4>(acc, net.Wt[l], R, Kk, nullptr, wave, lane);
         __syncthreads();
-        dgrad_epilogue<P, RT, PT>(acc, net, l, act, lda, wave, lane, mw, dsk);
+        dgrad_epilogue<RT, PT>(acc, net, l, v, wave, lane, mw, dsk);
         __syncthreads();
-        save_tile<P>(st, act, lda, TP, R, reinterpret_cast<T*>(a.dz[l]) + slot0 * R, net.Mt[l - 1] / P::KS);
+        v.template queue_save<4>(a.dz[l], slot0, 0, TP, R);
     }
 
     // ---- layer 0 dgrad + posenc / warp adjoint
-    warp_adjoint<P, TP>(net, a.geo, a.c2f.on, wsh, smem, lda, wave, lane, b, p0, red, red9, a.dH_partial, a.d_coords, st,
+    warp_adjoint<P, TP>(net, a.geo, a.c2f.on, wsh, smem, v.lda, wave, lane, b, p0, red, red9, a.dH_partial, a.d_coords, v.st,
                         nullptr, dsk);
 }
 

@@ -19,6 +19,11 @@
 // and rgb (12 B); reads target + mask (16 B).  Against the separate forward / loss / backward
 // kernels this drops the last layer's input (written and read back, 1 KB), rgb / d rgb round
 // trips and a second prologue.
+//
+// The kernel works on a TileView<P> (marf_gemm.h: a phase is written once over a tile view, a recipe
+// is a view).  The epilogues and the loss tail (step_target, step_loss_slots, step_tile_partials,
+// step_wlast_grad, step_fill_d) are the functions k_mlp_step_split runs over its split view; only the
+// last layer's MFMA loop is written out here, for its prefetched weight fragments.
 #include "marf_gemm.h"
 
 namespace marf {
@@ -42,7 +47,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void k_mlp_step(StepArgs 
     constexpr int RT = 8 / PT;
     static_assert(TP % (16 * NW) == 0, "last layer: whole 16-pixel groups per wave");
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    T* act = reinterpret_cast<T*>(smem);
     __shared__ float wsh[32];
     __shared__ float red[(NW * 64 > 2 * TP ? NW * 64 : 2 * TP) * 2];
     __shared__ float red9[NW * 9];
@@ -52,13 +56,12 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void k_mlp_step(StepArgs 
     __shared__ __attribute__((aligned(16))) float bsh[BL ? MARF_STEP_NBIAS : 4];  // forward biases
 
     const NetDev& net = a.net;
-    const int lda = a.lda;
+    TileView<P> v(smem, a.lda, TP);
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     int b, p0;
     long long slot0;
     tile_origin(a.geo, blockIdx.x, TP, b, p0, slot0);
     const int nl = net.n_layers;
-    const int Np = a.geo.Np;
 #ifdef MARF_STAMPS
     unsigned long long* sp = a.stamps ? a.stamps + (size_t)blockIdx.x * 32 : nullptr;
 #endif
@@ -71,30 +74,18 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void k_mlp_step(StepArgs 
         for (int l = 0, off = 0; l < nl - 1; off += net.Mp[l], ++l)
             for (int e = threadIdx.x; e < net.Mp[l]; e += 64 * NW) bsh[off + e] = net.bias[l][e];
     }
-    // target + mask of the tile's slots: loaded now, parked in gl until the loss needs them.
-    // Straight-line (every thread loads, padding slots a clamped valid pixel, zeroed after) so the
-    // compiler counts them and the barrier below waits for the band weights only.
-    float4 tg;
-    {
-        const int ti = threadIdx.x & (TP - 1);
-        const int pc = min(p0 + ti, Np - 1);
-        const float* gb = a.gt + (size_t)b * 3 * Np + pc;
-        const float* mb = a.mask ? a.mask + (size_t)b * Np + pc : gb;
-        tg = make_float4(gb[0], gb[Np], gb[2 * (size_t)Np], mb[0]);
-        if (!a.mask) tg.w = 1.0f;
-        if (p0 + ti >= Np) tg = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+    // target + mask of the tile's slots: loaded now, parked in gl until the loss needs them; the
+    // barrier below waits for the band weights only (step_target)
+    const float4 tg = step_target<TP>(a, b, p0);
     if ((int)threadIdx.x < net.L) wsh[threadIdx.x] = cw;
     __syncthreads();
     STAMP(19);
-    tile_prologue<P, TP, true, NW>(net, a.geo, a.c2f.on, wsh, act, lda, b, p0);
+    tile_prologue<P, TP, true, NW>(net, a.geo, a.c2f.on, wsh, v.act, v.lda, b, p0);
     if ((int)threadIdx.x < TP) st_as<float4>(&gl[threadIdx.x][0], tg);
     __syncthreads();
     STAMP(1);
     // every saved tile streams out during the GEMM that reads it next (TileStore)
-    TileStore<T> st;
-    save_tile<P, NW>(st, act, lda, TP, net.Kp[0], reinterpret_cast<T*>(a.feat[0]) + slot0 * net.Kp[0],
-                     net.Kp[0] / P::KS, MARF_DIAG_SAVE(net));
+    v.template queue_save<NW>(a.feat[0], slot0, 0, TP, net.Kp[0], MARF_DIAG_SAVE(net));
 
     // ---- hidden layers (forward); the last one is peeled so the last layer's weight fragments
     //      can be in flight behind its epilogue without pinning registers through the loop
@@ -104,220 +95,112 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void k_mlp_step(StepArgs 
         else return net.bias[l];
     };
     auto hidden = [&](int l) {
-        const int K = net.Kp[l], M = net.Mp[l], n_rt = M / 32;
+        const int K = net.Kp[l], M = net.Mp[l];
         f32x16 acc[RT][PT];
-        gemm_tile<P, RT, PT, NW>(acc, reinterpret_cast<const T*>(net.Wf[l]), K, n_rt, act, lda, wave, lane, bias_of(l), st);
+        v.template gemm<RT, PT, NW>(acc, net.Wf[l], M, K, bias_of(l), wave, lane);
         boff += M;
         __syncthreads();  // every wave has consumed the layer input
         STAMP(2 + 2 * l);
-        relu_epilogue<P, RT, PT, NW>(acc, act, lda, n_rt, wave, lane, a.mask_bits[l + 1], blockIdx.x, net.diag[l + 1]);
+        relu_epilogue<RT, PT, NW>(acc, v, M / 32, wave, lane, a.mask_bits[l + 1], blockIdx.x, net.diag[l + 1]);
         __syncthreads();
         if (l < 3) STAMP(3 + 2 * l);
         if (SK && ((net.skip >> (l + 1)) & 1u)) {  // skip layer: [feature ; posenc] (model/planar.py:440-441)
-            tile_prologue<P, TP, true, NW>(net, a.geo, a.c2f.on, wsh, act, lda, b, p0, M);
+            tile_prologue<P, TP, true, NW>(net, a.geo, a.c2f.on, wsh, v.act, v.lda, b, p0, M);
             __syncthreads();
         }
-        st.clear();
+        v.clear_save();
         if (l + 1 < nl - 1) {  // the last layer's input never leaves LDS
             const int Kn = net.Kp[l + 1];  // (M + Kp0 for a skip layer)
-            save_tile<P, NW>(st, act, lda, TP, Kn, reinterpret_cast<T*>(a.feat[l + 1]) + slot0 * Kn, Kn / P::KS,
-                             MARF_DIAG_SAVE(net));
+            v.template queue_save<NW>(a.feat[l + 1], slot0, 0, TP, Kn, MARF_DIAG_SAVE(net));
         }
     };
     for (int l = 0; l < nl - 2; ++l) hidden(l);
     constexpr int NWL = 8;  // prefetched last-layer k-steps (16x16 fragments)
     typename P::frag wl[NWL];
+    const T* Wlast = reinterpret_cast<const T*>(net.Wf[nl - 1]);
+    const int Kl = net.Kp[nl - 1];
+    const int nk16 = Kl / P::KS16;
     {
         const int l = nl - 2;
-        const int K = net.Kp[l], M = net.Mp[l], n_rt = M / 32;
+        const int K = net.Kp[l], M = net.Mp[l];
         f32x16 acc[RT][PT];
-        gemm_tile<P, RT, PT, NW>(acc, reinterpret_cast<const T*>(net.Wf[l]), K, n_rt, act, lda, wave, lane, bias_of(l), st);
+        v.template gemm<RT, PT, NW>(acc, net.Wf[l], M, K, bias_of(l), wave, lane);
         __syncthreads();
         STAMP(2 + 2 * l);
-        const T* W = reinterpret_cast<const T*>(net.Wf[nl - 1]);
-        const int nk16 = net.Kp[nl - 1] / P::KS16;
 #pragma unroll
-        for (int u = 0; u < NWL; ++u) wl[u] = P::load_frag(W + ((size_t)(u < nk16 ? u : 0) * 64 + lane) * P::FE);
-        relu_epilogue<P, RT, PT, NW>(acc, act, lda, n_rt, wave, lane, a.mask_bits[l + 1], blockIdx.x, net.diag[l + 1]);
+        for (int u = 0; u < NWL; ++u) wl[u] = P::load_frag(Wlast + ((size_t)(u < nk16 ? u : 0) * 64 + lane) * P::FE);
+        relu_epilogue<RT, PT, NW>(acc, v, M / 32, wave, lane, a.mask_bits[l + 1], blockIdx.x, net.diag[l + 1]);
         __syncthreads();
-        st.clear();
+        v.clear_save();
     }
 
-    // ---- last layer (3 outputs, rows padded to 16): 16x16 MFMA, TP/NW pixels per wave, sigmoid,
-    //      rgb, masked-MSE partial and d rgb, sigmoid backward -> gl
-    const int Kl = net.Kp[nl - 1];
+    // ---- last layer (3 outputs, rows padded to 16): mirrors last_layer_gemm (marf_gemm.h), written
+    //      out with the first NWL weight fragments prefetched above -- this kernel's scheduling alone;
+    //      through the view's w16 / mma16_row the 64-slot instantiations spilled one register more --
+    //      then sigmoid, rgb, masked-MSE partial and d rgb, sigmoid backward -> gl (step_loss_slots)
     {
-        const T* W = reinterpret_cast<const T*>(net.Wf[nl - 1]);
         constexpr int NJ = TP / NW / 16;
         f32x4 acc[NJ];
 #pragma unroll
         for (int j = 0; j < NJ; ++j) acc[j] = (f32x4){};
-        const int ko = P::kofs16(lane);
-        const int nk16 = Kl / P::KS16;
 #pragma unroll
         for (int u = 0; u < NWL; ++u) {
             if (u < nk16) {
 #pragma unroll
                 for (int j = 0; j < NJ; ++j) {
                     const int px = wave * (TP / NW) + j * 16 + (lane & 15);
-                    typename P::frag bb = P::load_frag(act + (size_t)px * lda + u * P::KS16 + ko);
+                    typename P::frag bb = P::load_frag(v.act + (size_t)px * v.lda + u * P::KS16 + P::kofs16(lane));
                     acc[j] = P::mma16(wl[u], bb, acc[j]);
                 }
             }
         }
         for (int u = NWL; u < nk16; ++u) {
-            typename P::frag wa = P::load_frag(W + ((size_t)u * 64 + lane) * P::FE);
+            typename P::frag wa = P::load_frag(Wlast + ((size_t)u * 64 + lane) * P::FE);
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
                 const int px = wave * (TP / NW) + j * 16 + (lane & 15);
-                typename P::frag bb = P::load_frag(act + (size_t)px * lda + u * P::KS16 + ko);
+                typename P::frag bb = P::load_frag(v.act + (size_t)px * v.lda + u * P::KS16 + P::kofs16(lane));
                 acc[j] = P::mma16(wa, bb, acc[j]);
             }
         }
-        if (lane < 16) {
-            const float* bl = net.bias[nl - 1];
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                const int px = wave * (TP / NW) + j * 16 + lane;
-                const int p = p0 + px;
-                float g[3] = {0.f, 0.f, 0.f};
-                float sq = 0.f, mv = 0.f;
-                const float4 tv = ld_as<float4>(&gl[px][0]);  // prefetched target, mask
-                const float tgt[3] = {tv.x, tv.y, tv.z};
-                if (p < Np) {
-                    const float m = tv.w;
-                    float* o = a.rgb ? a.rgb + ((size_t)b * Np + p) * 3 : nullptr;
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        const float z = acc[j][c] + bl[c];
-                        const float y = 1.0f / (1.0f + expf(-z));
-                        if (o) o[c] = y;
-                        // model/planar.py:388-390 and its autograd: x = (p - g) m, d = 2 x m
-                        const float x = (y - tgt[c]) * m;
-                        sq += x * x;
-                        const float d = (2.0f * x) * m;
-                        g[c] = (d * (1.0f - y)) * y;  // torch sigmoid_backward
-                    }
-                    mv = m;
-                }
-                st_as<float4>(&gl[px][0], make_float4(g[0], g[1], g[2], 0.f));
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {  // g = hi + lo (bf16 pair: ~16 significant bits)
-                    const T hi = P::cvt(g[c]);
-                    gT[c][px] = hi;
-                    gT[4 + c][px] = P::cvt(g[c] - P::tof(hi));
-                }
-                gT[3][px] = P::cvt(0.f);
-                gT[7][px] = P::cvt(0.f);
-                lsum[0][px] = sq;
-                lsum[1][px] = mv;
-            }
-        }
+        step_loss_slots<P, TP, NW>(a, acc, wave, lane, b, p0, gl, gT, lsum);
     }
     __syncthreads();
 
     STAMP(9);
-    // ---- masked-MSE partial of the tile (fp64, fixed order) and the last bias gradient
-    if (wave == 0) {
-        double s0 = 0.0, s1 = 0.0;
-        for (int px = lane; px < TP; px += 64) {
-            s0 += (double)lsum[0][px];
-            s1 += (double)lsum[1][px];
-        }
-        s0 = wave_total63(s0);
-        s1 = wave_total63(s1);
-        if (lane == 63) {
-            a.loss_partial[2 * (size_t)blockIdx.x] = s0;
-            a.loss_partial[2 * (size_t)blockIdx.x + 1] = s1;
-        }
-    } else if (wave == 1) {
-        float s[3] = {0.f, 0.f, 0.f};
-        for (int px = lane; px < TP; px += 64)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) s[c] += gl[px][c];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float t = wave_total63(s[c]);
-            if (lane == 63) a.blast_partial[(size_t)blockIdx.x * 3 + c] = t;
-        }
-    }
-
-    // ---- last-layer weight gradient of the tile: dW[c][k] = sum_px g[px][c] feat[px][k]
-    //      16x16 MFMA, A = g^T (rows 0-2: bf16 hi parts of the 3 channels, rows 4-6: lo parts),
-    //      B = feat (pixels x features, transposed LDS read for bf16); hi + lo rows are added
-    //      after the K loop.  Column tiles of 16 features dealt round-robin to the waves.
-    {
-        float* wout = a.wlast_partial + (size_t)blockIdx.x * 3 * Kl;
-        for (int ct = wave; ct < Kl / 16; ct += NW) {
-            f32x4 acc = (f32x4){};
-            if constexpr (sizeof(T) == 2) {
-                const int g = lane >> 4, gi = lane & 15;
-#pragma unroll
-                for (int k0 = 0; k0 < TP; k0 += 32) {
-                    typename P::frag fa;
-                    if (gi < 8) fa = P::load_frag(&gT[gi][k0 + 8 * g]);
-                    else fa = (typename P::frag){};
-                    const int r0 = k0 + 8 * g + (gi >> 2);
-                    const u16* base = act + (size_t)r0 * lda + ct * 16 + 4 * (gi & 3);
-                    acc = P::mma16(fa, frag_of<typename P::frag>(tr_read16(base), tr_read16(base + 4 * lda)), acc);
-                }
-            } else {
-                const int kk = lane >> 4, n = lane & 15;
-                for (int k0 = 0; k0 < TP; k0 += 4) {
-                    const float fa = n < 8 ? P::tof(gT[n][k0 + kk]) : 0.f;
-                    const float fb = P::tof(act[(size_t)(k0 + kk) * lda + ct * 16 + n]);
-                    acc = P::mma16(fa, fb, acc);
-                }
-            }
-            // accumulator: lane l, reg r -> row 4 (l >> 4) + r, column l & 15: hi rows in lanes
-            // 0-15, lo rows in lanes 16-31
-            float lo[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) lo[c] = __shfl_down(acc[c], 16, 64);
-            if (lane < 16) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) wout[(size_t)c * Kl + ct * 16 + lane] = acc[c] + lo[c];
-            }
-        }
-    }
+    step_tile_partials<TP>(a, wave, lane, gl, lsum);
+    step_wlast_grad<P, TP, NW>(a, Kl, v.feat(), v.lda, wave, lane, gT);
     __syncthreads();  // feat_{n-1} consumed
 
-    // ---- d (last-layer input) operand: act[px][0 .. Mt) = g
-    if ((int)threadIdx.x < TP) {
-        const int i = threadIdx.x;
-        T* row = act + (size_t)i * lda;
-        const int Kt = net.Mt[nl - 1];
-        for (int c = 0; c < Kt; ++c) row[c] = P::cvt(c < 3 ? MARF_DIAG_ROUND(gl[i][c], net.diag[nl - 1], 3) : 0.f);
-    }
+    step_fill_d<TP>(v, gl, net.Mt[nl - 1], net.diag[nl - 1]);
     STAMP(10);
     __syncthreads();
 
     // ---- dgrad chain, l = n-1 .. 1 : dfeat_l = W_l^T dz_{l+1}; dz_l = dfeat_l * relu'(feat_l)
-    st.clear();
+    v.clear_save();
     float* dsk = nullptr;  // skip nets: the posenc gradient of the skip layers
     if (SK && net.skip) {
-        dsk = reinterpret_cast<float*>(smem + skip_lds_off<P, TP>(net, lda));
+        dsk = reinterpret_cast<float*>(smem + skip_lds_off<P, TP>(net, v.lda));
         for (int e = threadIdx.x; e < TP * net.Kp[0]; e += 64 * NW) dsk[e] = 0.f;
     }
     for (int l = nl - 1; l >= 1; --l) {
-        const int R = net.Kp[l], Kk = net.Mt[l], n_rt = R / 32;
+        const int R = net.Kp[l], Kk = net.Mt[l];
         f32x16 acc[RT][PT];
         const uint4 mw = *mask_record(a.mask_bits[l], blockIdx.x, wave, lane, NW);  // in flight behind the GEMM
-        gemm_tile<P, RT, PT, NW>(acc, reinterpret_cast<const T*>(net.Wt[l]), Kk, n_rt, act, lda, wave, lane, nullptr, st);
+        v.template gemm<RT, PT, NW>(acc, net.Wt[l], R, Kk, nullptr, wave, lane);
         __syncthreads();
-        dgrad_epilogue<P, RT, PT, NW>(acc, net, l, act, lda, wave, lane, mw, dsk);
+        dgrad_epilogue<RT, PT, NW>(acc, net, l, v, wave, lane, mw, dsk);
         __syncthreads();
         if (l <= 4) STAMP(15 - l);  // 14 .. 11
-        save_tile<P, NW>(st, act, lda, TP, R, reinterpret_cast<T*>(a.dz[l]) + slot0 * R, net.Mt[l - 1] / P::KS,
-                         MARF_DIAG_SAVE(net));
+        v.template queue_save<NW>(a.dz[l], slot0, 0, TP, R, MARF_DIAG_SAVE(net));
     }
 
     // ---- layer-0 dgrad + posenc / warp adjoint -> dH partial
 #ifdef MARF_STAMPS
-    warp_adjoint<P, TP, true, NW>(net, a.geo, a.c2f.on, wsh, smem, lda, wave, lane, b, p0, red, red9, a.dH_partial, nullptr, st, sp,
-                                  dsk);
+    warp_adjoint<P, TP, true, NW>(net, a.geo, a.c2f.on, wsh, smem, v.lda, wave, lane, b, p0, red, red9, a.dH_partial, nullptr, v.st,
+                                  sp, dsk);
 #else
-    warp_adjoint<P, TP, true, NW>(net, a.geo, a.c2f.on, wsh, smem, lda, wave, lane, b, p0, red, red9, a.dH_partial, nullptr, st,
+    warp_adjoint<P, TP, true, NW>(net, a.geo, a.c2f.on, wsh, smem, v.lda, wave, lane, b, p0, red, red9, a.dH_partial, nullptr, v.st,
                                   nullptr, dsk);
 #endif
     STAMP(15);

@@ -1,7 +1,9 @@
 // marf_step_split.hip -- the fused training step (and its forward-only render) of MARF_BF16X3 nets
 // that the pixel-per-wave kernel k_step2 cannot hold: more than 5 layers, or hidden widths above 256
-// (up to 512).  k_mlp_step's phases (marf_step.hip) on the all-operands-split tile blocks of
-// marf_gemm.h: the LDS tile is two bf16 planes [TP][lda] (hi, then lo), every weight image is hi
+// (up to 512).  k_mlp_step's phases (marf_step.hip) over the split tile view of marf_gemm.h
+// (SplitView<false>; a phase is written once over a view, a recipe is a view -- the epilogues, the
+// last layer and the loss tail here are the functions k_mlp_step runs, only the prologue is this
+// unit's own): the LDS tile is two bf16 planes [TP][lda] (hi, then lo), every weight image is hi
 // then lo, and every GEMM is W_h a_h + W_h a_l + W_l a_h into one fp32 accumulator:
 //
 //   forward   z = W_h a_h + W_h a_l + W_l a_h (+ bias as the accumulators' start); a' = relu(z) split;
@@ -65,6 +67,7 @@ __global__ __launch_bounds__(256, 1) void k_mlp_step_split(StepArgs a) {
     constexpr int NW = 4;
     constexpr int PT = TP / 32;
     constexpr int RT = 8 / PT;
+    constexpr int NJ = TP / NW / 16;
     constexpr int TS = FWD ? 1 : TP;  // the training-only arrays
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ float wsh[32];
@@ -75,219 +78,81 @@ __global__ __launch_bounds__(256, 1) void k_mlp_step_split(StepArgs a) {
     __shared__ float lsum[2][TS];                              // per-slot ((p-g) m)^2 and m
 
     const NetDev& net = a.net;
-    const int lda = a.lda;
-    u16* ah = reinterpret_cast<u16*>(smem);
-    u16* al = ah + (size_t)TP * lda;
+    SplitView<false> v(smem, a.lda, TP);  // saved tiles: the hi plane only
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     int b, p0;
     long long slot0;
     tile_origin(a.geo, blockIdx.x, TP, b, p0, slot0);
     const int nl = net.n_layers;
-    const int Np = a.geo.Np;
 
     // target + mask of the tile's slots: loaded now, parked in gl until the loss needs them
-    // (every thread loads, padding slots a clamped valid pixel, zeroed after: as k_mlp_step)
     float4 tg = make_float4(0.f, 0.f, 0.f, 0.f);
     if constexpr (FWD) {
         c2f_weights_lds(a.c2f, net.L, wsh);
     } else {
         if ((int)threadIdx.x < net.L) wsh[threadIdx.x] = a.c2f_w[threadIdx.x];
-        const int ti = threadIdx.x & (TP - 1);
-        const int pc = min(p0 + ti, Np - 1);
-        const float* gb = a.gt + (size_t)b * 3 * Np + pc;
-        const float* mb = a.mask ? a.mask + (size_t)b * Np + pc : gb;
-        tg = make_float4(gb[0], gb[Np], gb[2 * (size_t)Np], mb[0]);
-        if (!a.mask) tg.w = 1.0f;
-        if (p0 + ti >= Np) tg = make_float4(0.f, 0.f, 0.f, 0.f);
+        tg = step_target<TP>(a, b, p0);
     }
     __syncthreads();
-    tile_prologue_split<TP, !FWD>(net, a.geo, a.c2f.on, wsh, ah, al, lda, b, p0);
+    tile_prologue_split<TP, !FWD>(net, a.geo, a.c2f.on, wsh, v.hi, v.lo, v.lda, b, p0);
     if constexpr (!FWD) {
         if ((int)threadIdx.x < TP) st_as<float4>(&gl[threadIdx.x][0], tg);
     }
     __syncthreads();
 
-    // the saved tiles: hi plane only (stl stays idle), streamed out after the GEMM that reads the tile
-    TileStore<u16> sth, stl;
-    sth.clear();
-    stl.clear();
-    auto save_hi = [&](void* dst, int cols) {
-        if constexpr (!FWD) sth.init(lda, reinterpret_cast<u16*>(dst) + slot0 * cols, cols, TP, cols, wave, lane, NW);
+    // the saved tiles stream out after the GEMM that reads the tile
+    auto save = [&](void* dst, int cols) {
+        if constexpr (!FWD) v.template queue_save<NW>(dst, slot0, 0, TP, cols);
     };
-    save_hi(a.feat[0], net.Kp[0]);
+    save(a.feat[0], net.Kp[0]);
 
     // ---- hidden layers (forward)
     for (int l = 0; l < nl - 1; ++l) {
         const int K = net.Kp[l], M = net.Mp[l];
         f32x16 acc[RT][PT];
-        gemm_tile_split<RT, PT, NW>(acc, reinterpret_cast<const u16*>(net.Wf[l]), M, K, ah, al, lda, wave, lane, net.bias[l],
-                                    sth, stl);
+        v.template gemm<RT, PT, NW>(acc, net.Wf[l], M, K, net.bias[l], wave, lane);
         __syncthreads();  // every wave has consumed the layer input
-        relu_epilogue_split<RT, PT, NW>(acc, ah, al, lda, M / 32, wave, lane, FWD ? nullptr : a.mask_bits[l + 1], blockIdx.x);
+        relu_epilogue<RT, PT, NW>(acc, v, M / 32, wave, lane, FWD ? nullptr : a.mask_bits[l + 1], blockIdx.x);
         __syncthreads();
-        sth.clear();
-        if (l + 1 < nl - 1) save_hi(a.feat[l + 1], M);  // the last layer's input never leaves LDS
+        v.clear_save();
+        if (l + 1 < nl - 1) save(a.feat[l + 1], M);  // the last layer's input never leaves LDS
     }
 
     // ---- last layer (3 outputs, rows padded to 16): 16x16 MFMA in the same three terms, TP/NW pixels
-    //      per wave, then sigmoid, rgb, masked-MSE partial, d rgb and sigmoid backward in fp32
+    //      per wave, then sigmoid (render: to rgb) and the loss tail shared with k_mlp_step, in fp32
     const int Kl = net.Kp[nl - 1];
-    {
-        const u16* Wh = reinterpret_cast<const u16*>(net.Wf[nl - 1]);
-        const u16* Wl = Wh + (size_t)16 * Kl;
-        constexpr int NJ = TP / NW / 16;
-        f32x4 acc[NJ];
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) acc[j] = (f32x4){};
-        const int ko = P::kofs16(lane);
-        for (int k0 = 0; k0 < Kl; k0 += P::KS16) {
-            const size_t wo = ((size_t)(k0 / P::KS16) * 64 + lane) * P::FE;
-            const P::frag wh = P::load_frag(Wh + wo), wl = P::load_frag(Wl + wo);
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                const int px = wave * (TP / NW) + j * 16 + (lane & 15);
-                const size_t bo = (size_t)px * lda + k0 + ko;
-                const P::frag bh = P::load_frag(ah + bo), bl = P::load_frag(al + bo);
-                acc[j] = P::mma16(wh, bh, acc[j]);
-                acc[j] = P::mma16(wh, bl, acc[j]);
-                acc[j] = P::mma16(wl, bh, acc[j]);
-            }
-        }
-        if (lane < 16) {
-            const float* bl = net.bias[nl - 1];
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                const int px = wave * (TP / NW) + j * 16 + lane;
-                const int p = p0 + px;
-                if constexpr (FWD) {
-                    if (p < Np) {
-                        float* o = a.rgb + ((size_t)b * Np + p) * 3;
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) {
-                            const float z = acc[j][c] + bl[c];
-                            o[c] = 1.0f / (1.0f + expf(-z));
-                        }
-                    }
-                } else {
-                    float g[3] = {0.f, 0.f, 0.f};
-                    float sq = 0.f, mv = 0.f;
-                    const float4 tv = ld_as<float4>(&gl[px][0]);  // prefetched target, mask
-                    const float tgt[3] = {tv.x, tv.y, tv.z};
-                    if (p < Np) {
-                        const float m = tv.w;
-                        float* o = a.rgb ? a.rgb + ((size_t)b * Np + p) * 3 : nullptr;
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) {
-                            const float z = acc[j][c] + bl[c];
-                            const float y = 1.0f / (1.0f + expf(-z));
-                            if (o) o[c] = y;
-                            // model/planar.py:388-390 and its autograd: x = (p - g) m, d = 2 x m
-                            const float x = (y - tgt[c]) * m;
-                            sq += x * x;
-                            const float d = (2.0f * x) * m;
-                            g[c] = (d * (1.0f - y)) * y;  // torch sigmoid_backward
-                        }
-                        mv = m;
-                    }
-                    st_as<float4>(&gl[px][0], make_float4(g[0], g[1], g[2], 0.f));
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) split1(g[c], gT[c][px], gT[4 + c][px]);
-                    gT[3][px] = 0;
-                    gT[7][px] = 0;
-                    lsum[0][px] = sq;
-                    lsum[1][px] = mv;
-                }
-            }
-        }
-    }
-    if constexpr (!FWD) {
-        __syncthreads();
-
-        // ---- masked-MSE partial of the tile (fp64, fixed order) and the last bias gradient
-        if (wave == 0) {
-            double s0 = 0.0, s1 = 0.0;
-            for (int px = lane; px < TP; px += 64) {
-                s0 += (double)lsum[0][px];
-                s1 += (double)lsum[1][px];
-            }
-            s0 = wave_total63(s0);
-            s1 = wave_total63(s1);
-            if (lane == 63) {
-                a.loss_partial[2 * (size_t)blockIdx.x] = s0;
-                a.loss_partial[2 * (size_t)blockIdx.x + 1] = s1;
-            }
-        } else if (wave == 1) {
-            float s[3] = {0.f, 0.f, 0.f};
-            for (int px = lane; px < TP; px += 64)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) s[c] += gl[px][c];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float t = wave_total63(s[c]);
-                if (lane == 63) a.blast_partial[(size_t)blockIdx.x * 3 + c] = t;
-            }
-        }
-
-        // ---- last-layer weight gradient of the tile, as k_mlp_step: dW[c][k] = sum_px g[px][c]
-        //      a_h[px][k]; A = g^T (rows 0-2 hi, rows 4-6 lo), B = the hi plane (transposed LDS read)
+    if constexpr (FWD) {
+        last_layer_fwd<TP, NW, 3>(v, net, wave, lane, b, p0, a.geo.Np, a.rgb);
+    } else {
         {
-            float* wout = a.wlast_partial + (size_t)blockIdx.x * 3 * Kl;
-            const int g = lane >> 4, gi = lane & 15;
-            for (int ct = wave; ct < Kl / 16; ct += NW) {
-                f32x4 acc = (f32x4){};
-#pragma unroll
-                for (int k0 = 0; k0 < TP; k0 += 32) {
-                    P::frag fa;
-                    if (gi < 8) fa = P::load_frag(&gT[gi][k0 + 8 * g]);
-                    else fa = (P::frag){};
-                    const int r0 = k0 + 8 * g + (gi >> 2);
-                    const u16* base = ah + (size_t)r0 * lda + ct * 16 + 4 * (gi & 3);
-                    acc = P::mma16(fa, frag_of<P::frag>(tr_read16(base), tr_read16(base + 4 * lda)), acc);
-                }
-                // accumulator: lane l, reg r -> row 4 (l >> 4) + r, column l & 15: hi rows in lanes
-                // 0-15, lo rows in lanes 16-31
-                float lo[3];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) lo[c] = __shfl_down(acc[c], 16, 64);
-                if (lane < 16) {
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) wout[(size_t)c * Kl + ct * 16 + lane] = acc[c] + lo[c];
-                }
-            }
+            f32x4 acc[NJ];
+            last_layer_gemm<TP, NW>(v, net.Wf[nl - 1], Kl, wave, lane, acc);
+            step_loss_slots<P, TP, NW>(a, acc, wave, lane, b, p0, gl, gT, lsum);
         }
+        __syncthreads();
+        step_tile_partials<TP>(a, wave, lane, gl, lsum);
+        step_wlast_grad<P, TP, NW>(a, Kl, v.feat(), v.lda, wave, lane, gT);  // B = the hi plane
         __syncthreads();  // feat_{n-1} consumed
-
-        // ---- d (last-layer input) operand: both planes' columns 0 .. Mt) = g split
-        if ((int)threadIdx.x < TP) {
-            const int i = threadIdx.x;
-            const size_t at = (size_t)i * lda;
-            const int Kt = net.Mt[nl - 1];
-            for (int c = 0; c < Kt; ++c) {
-                ah[at + c] = c < 3 ? gT[c][i] : (u16)0;
-                al[at + c] = c < 3 ? gT[4 + c][i] : (u16)0;
-            }
-        }
+        step_fill_d<TP>(v, gl, net.Mt[nl - 1], 0);
         __syncthreads();
 
         // ---- dgrad chain, l = n-1 .. 1 : da = W_h^T dz_h + W_h^T dz_l + W_l^T dz_h; dz_l = da * relu'
-        sth.clear();
+        v.clear_save();
         for (int l = nl - 1; l >= 1; --l) {
             const int R = net.Kp[l], Kk = net.Mt[l];
             f32x16 acc[RT][PT];
             const uint4 mw = *mask_record(a.mask_bits[l], blockIdx.x, wave, lane, NW);  // in flight behind the GEMM
-            gemm_tile_split<RT, PT, NW>(acc, reinterpret_cast<const u16*>(net.Wt[l]), R, Kk, ah, al, lda, wave, lane, nullptr,
-                                        sth, stl);
+            v.template gemm<RT, PT, NW>(acc, net.Wt[l], R, Kk, nullptr, wave, lane);
             __syncthreads();
-            mask_epilogue_split<RT, PT, NW>(acc, ah, al, lda, R / 32, wave, lane, mw);
+            mask_epilogue<RT, PT, NW>(acc, v, R / 32, wave, lane, mw);
             __syncthreads();
-            save_hi(a.dz[l], R);
+            save(a.dz[l], R);
         }
 
         // ---- layer-0 dgrad (three terms; dz_1's stores go out behind it) + posenc / warp adjoint in
         //      fp32 -> dH partial
         f32x16 acc[RT][PT];
-        gemm_tile_split<RT, PT, NW>(acc, reinterpret_cast<const u16*>(net.Wt[0]), net.Kp[0], net.Mt[0], ah, al, lda, wave,
-                                    lane, nullptr, sth, stl);
+        v.template gemm<RT, PT, NW>(acc, net.Wt[0], net.Kp[0], net.Mt[0], nullptr, wave, lane);
         __syncthreads();
         warp_adjoint_tail<P, TP, true, NW, false>(acc, net, a.geo, a.c2f.on, wsh, smem, wave, lane, b, p0, red, red9,
                                                   a.dH_partial, nullptr, nullptr, nullptr);

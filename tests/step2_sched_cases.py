@@ -11,6 +11,11 @@ tile both occur, and the dgrad runs with a sink set.
 The tile-* cases pin the tile kernels (plain bf16, fp32, fp16, one skip net) in the same way; their
 digests come from a build of the commit named under "tile_cases" in the fixture.  No candidate case
 had to be left out: the parent library reproduced every one in three separate processes.
+
+The split-*, plain-fwd-bwd, render-* and mask-* cases ("tile_view_cases" in the fixture, with their
+parent commit) pin what had no bit fixture before the tile phases were written once over a tile view:
+the split tile step k_mlp_step_split and its render, the separate k_mlp_fwd / k_mlp_bwd path and the
+mask network's kernels in both recipes.  Kept on the same rule; none had to be left out.
 """
 import hashlib
 import os
@@ -50,7 +55,27 @@ CASES = {
     "tile-fp32": (1, 64, 64, 8, FULL, {}, {"precision": "fp32"}),
     "tile-fp16": (1, 64, 64, 16, FULL, {}, {"precision": "fp16"}),
     "tile-skip": (1, 64, 64, 8, FULL, {}, {"precision": "bf16", "skip": [2]}),
+    # k_mlp_step_split (bf16x3 on nets k_step2 cannot hold).  TP = 128: six layers force the tile
+    # kernel, one row tile per wave
+    "split-tp128": (1, 64, 64, 8, [128] * 6, {}, {}),
+    # TP = 64 (width above 256), four row tiles per wave: the 2-deep ring of gemm_rows_split
+    "split-tp64-ring": (1, 64, 64, 16, [512] * 2, {}, {}),
+    # 288 = 9 x 32: waves get 3 and 2 row tiles; 9 k-steps: the GEMM's remainder
+    "split-odd": (1, 64, 64, 8, [288, 512, 288], {}, {}),
+    # 2,700 pixels per patch: the last tile of each patch is partly padding
+    "split-pad": (2, 50, 54, 8, [128] * 6, {}, {}),
+    # k_mlp_fwd + k_mlp_bwd: the differentiable forward / backward path (no fused step).  No fixture
+    # of test_gpu_parity.py pinned their bits: its fused-against-separate test compares two paths of
+    # one build
+    "plain-fwd-bwd": (1, 64, 64, 8, FULL, {}, {"precision": "bf16", "fused_step": False}),
 }
+# the FWD instantiation of k_mlp_step_split: Model.predict_entire_image of the 6 x 128 net on a
+# 45 x 61 canvas (2,745 pixels: no multiple of 128)
+RENDER_CASES = {"render-deep": (45, 61, 8, [128] * 6)}
+# the mask network (k_mask_fwd / k_mask_bwd, fp32 and the all-operands-split recipe) on the seeded
+# cases of mask_split_ref.py: m and every parameter gradient of marf_hip.mask_forward + backward
+MASK_CASES = {f"mask-{prec}-{shape}": (prec, shape) for prec in ("fp32", "bf16x3a") for shape in ("ragged", "tiny", "exact")}
+ALL_CASES = list(CASES) + list(RENDER_CASES) + list(MASK_CASES)
 
 
 def build(case, setenv, out="/tmp/marf_sched"):
@@ -83,11 +108,13 @@ def build(case, setenv, out="/tmp/marf_sched"):
     return m, edict(idx=torch.arange(B), images=m.images)
 
 
-def step(m, var):
+def step(m, var, info=None):
     """rgb, loss, every MLP gradient and bias gradient, and d warp of one fused step (the state is
-    left as it was)."""
+    left as it was).  info["fused"]: whether the forward ran the fused step kernel."""
     m.optim.zero_grad()
     v = m.graph.forward(var, mode="train")
+    if info is not None:
+        info["fused"] = v.fused_loss is not None
     loss = m.summarize_loss(m.graph.compute_loss(v, mode="train"))
     loss.all.backward()
     out = {"rgb": v.rgb_prediction.detach().clone(), "loss": loss.rgb.detach().reshape(1).clone(),
@@ -103,10 +130,53 @@ def digest(t):
     return hashlib.sha1(a.view(torch.uint8).numpy().tobytes()).hexdigest()
 
 
+def render_bits(case, out="/tmp/marf_sched"):
+    from model import planar
+    H, W, L, hidden = RENDER_CASES[case]
+    opt = step_bits._opt(out, H=H, W=W, patch_H=32, patch_W=32, batch_size=2, use_edges=False,
+                         arch={"layers": [None] + list(hidden) + [3], "skip": [], "posenc": {"L_2D": L}})
+    torch.manual_seed(3)
+    m = planar.Model(opt)
+    m.build_networks()
+    m.graph.neural_image.progress.data.fill_(0.2)
+    kernel = m.graph.neural_image.engine(torch.device(DEV)).net.step_kernel
+    img = m.predict_entire_image()
+    assert tuple(img.shape) == (3, H, W) and torch.isfinite(img).all(), case
+    return {"kernel": kernel, "bits": {"rgb": digest(img)}}
+
+
+def mask_bits(case):
+    import marf_hip
+    import mask_split_ref as sr
+    from mask_common import MASK_PARAM_NAMES
+    prec, shape = MASK_CASES[case]
+    B, ph, pw = sr.SHAPES[shape]
+    c = sr.case(shape)
+    code = {"fp32": marf_hip.MARF_FP32, "bf16x3a": marf_hip.MARF_BF16X3A}[prec]
+    eng = marf_hip.MaskEngine(sr.N_VOCAB, code, 2 * ph, 2 * pw, ph, pw)
+    ps = [p.to(DEV).requires_grad_() for p in c["params"]]
+    m = marf_hip.mask_forward(eng, c["index"].to(torch.int32).to(DEV), c["embed"].to(DEV), ps)
+    m.backward(c["dm"].to(DEV))
+    torch.cuda.synchronize()
+    out = {"m": m.detach()}
+    out.update({name: p.grad for name, p in zip(MASK_PARAM_NAMES, ps)})
+    assert all(torch.isfinite(v).all() for v in out.values()), case
+    return {"kernel": "k_mask_fwd+k_mask_bwd " + prec, "bits": {k: digest(v) for k, v in out.items()}}
+
+
 def case_bits(case, setenv):
-    """{"kernel": the step kernel's name, "bits": {tensor: sha1 of its bytes}} of one step of `case`."""
+    """{"kernel": the step kernel's name, "bits": {tensor: sha1 of its bytes}} of one step of `case`
+    (of the render / the mask network's forward + backward for those cases)."""
+    if case in RENDER_CASES:
+        return render_bits(case)
+    if case in MASK_CASES:
+        return mask_bits(case)
     m, var = build(case, setenv)
     kernel = m.graph.neural_image.engine(torch.device(DEV)).net.step_kernel
-    out = step(m, var)
+    info = {}
+    out = step(m, var, info)
     assert all(torch.isfinite(v).all() for v in out.values()), case
+    if not CASES[case][6].get("fused_step", True):  # the separate kernels ran, not the net's step kernel
+        assert not info["fused"], case
+        kernel = "k_mlp_fwd+k_mlp_bwd"
     return {"kernel": kernel, "bits": {k: digest(v) for k, v in out.items()}}

@@ -18,10 +18,10 @@ import step2_sched_cases as sc
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("case", list(sc.CASES))
+@pytest.mark.parametrize("case", sc.ALL_CASES)
 def test_step_bits_equal_parent(case, monkeypatch):
-    """rgb, loss, every MLP gradient and bias gradient and d warp of one fused step: the digests of
-    the parent commit's library."""
+    """rgb, loss, every MLP gradient and bias gradient and d warp of one fused step (the render's rgb;
+    the mask network's m and parameter gradients): the digests of the parent commit's library."""
     ref = json.load(open(sc.BITS_JSON))["cases"][case]
     got = sc.case_bits(case, monkeypatch.setenv)
     assert got["kernel"] == ref["kernel"], (case, got["kernel"], ref["kernel"])

@@ -24,7 +24,7 @@ def main():
     import marf_hip
     import step2_sched_cases as sc
     out, commit = sys.argv[1], sys.argv[2]
-    cases = sys.argv[3:] or list(sc.CASES)
+    cases = sys.argv[3:] or sc.ALL_CASES
     res = {"source_hash": marf_hip.lib().marf_source_hash().decode(), "commit": commit, "cases": {}}
     for c in cases:
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--case", c], capture_output=True, text=True,
