@@ -961,8 +961,8 @@ static bool l0_recompute(const marf_net* n, const GeoDev& g, long long S) {
     if (e && e[0] == '0') return false;
     if ((n->s2.variant != 1 && n->s2.variant != 3) || g.mode != MARF_GEO_GRID) return false;
     const long long chunk = wgrad_chunk(S);
-    return marf_wgrad_l0_recompute_ok(n->Mp[0], n->Kp[1], n->s2.ldf0, S, (int)chunk, (int)((S + chunk - 1) / chunk),
-                                      g.Np_pad);
+    return marf_wgrad_l0_recompute_ok(n->Mp[0], n->Kp[1], n->s2.ldf0, n->L, S, (int)chunk,
+                                      (int)((S + chunk - 1) / chunk), g.Np_pad);
 }
 
 // The weight gradient of the last hidden layer (n-2) recomputes dz_{n-1} = relu'(z) (W_{n-1}^T g), a
@@ -1027,7 +1027,7 @@ static void plan_pipe(const marf_net* n, const GeoDev& g, long long S, int n_til
     if (!marf_wgrad_range_ok(n->kdt, n->Mp[0], n->Kp[1], q.ldf0, q.ldf0)) return;
     if (l0_recompute(n, g, S)) {  // the recomputing kernel's ranges may span only a few patches
         const long long mx = rup((long long)piece * q.TPX / R + 32, 32);
-        if (!marf_wgrad_l0_recompute_ok(n->Mp[0], n->Kp[1], q.ldf0, S, (int)mx, P * cus, g.Np_pad)) return;
+        if (!marf_wgrad_l0_recompute_ok(n->Mp[0], n->Kp[1], q.ldf0, n->L, S, (int)mx, P * cus, g.Np_pad)) return;
     }
     pp.on = 1;
     pp.G = G;
@@ -1395,7 +1395,7 @@ static int step2_backward(const marf_net* net, const marf_geometry* geo, const v
             x.kmap = l == 0 ? kmap : nullptr;
             if (p.dzl && l == nl - 2) x.dzl = dzl_src;
         }
-        if (marf_wgrad_fused_ok(Lf, nf, p.S, (int)chunk, n_chunks, g.Np_pad)) {
+        if (marf_wgrad_fused_ok(Lf, nf, p.S, (int)chunk, n_chunks, g.Np_pad, net->L)) {
             PipeStreams* st = nullptr;
             rc = pipe_streams(&st);
             if (rc) return rc;

@@ -201,7 +201,9 @@ struct WgDzlSrc {
 };
 // the shape the recomputing instantiation takes: a 256 x 256 bf16 T16 layer on the LDS-DMA kernel
 bool marf_wgrad_dzl_ok(int M, int ldz, int K, int ldf, long long S, int chunk, int n_chunks);
-bool marf_wgrad_l0_recompute_ok(int M, int ldz, int ldf0, long long S, int chunk, int n_chunks, long long Np_pad);
+// (L: the net's posenc bands; feat_0 is recomputed for L <= 16 only)
+bool marf_wgrad_l0_recompute_ok(int M, int ldz, int ldf0, int L, long long S, int chunk, int n_chunks,
+                                long long Np_pad);
 hipError_t marf_launch_wgrad_l0_recompute(const void* dz, int ldz, const GeoDev& geo, const float* c2f_w, int L,
                                           int nk0, int K0, long long S, int M, int chunk, int n_chunks, float* partial,
                                           float* bpartial, hipStream_t s, const WgRange* rng = nullptr, int dtype = 1);
@@ -230,7 +232,7 @@ struct WgFusedLayer {
 // s2 (fork / join events), then every layer's reduction in one launch on s; false if a shape does
 // not qualify
 bool marf_wgrad_fused_ok(const WgFusedLayer* layers, int n_layers, long long S, int chunk, int n_chunks,
-                         long long Np_pad);
+                         long long Np_pad, int L_bands);
 hipError_t marf_launch_wgrad_fused(const WgFusedLayer* layers, int n_layers, long long S, int chunk, int n_chunks,
                                    const GeoDev& f0_geo, const float* c2f_w, int L, int nk0, const float* gscale,
                                    const float* denom, hipStream_t s, hipStream_t s2, hipEvent_t fork, hipEvent_t join,

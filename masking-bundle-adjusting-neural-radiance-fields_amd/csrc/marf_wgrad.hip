@@ -1184,9 +1184,13 @@ bool marf_wgrad_dzl_ok(int M, int ldz, int K, int ldf, long long S, int chunk, i
 // Layer-0 weight gradient with feat_0 recomputed on chip (step kernel's feat0_recompute); bf16,
 // 256-wide layer 0, the 64-wide feat_0 of L <= 12 or the 96-wide one of L = 13..16 (both built in
 // the 96-wide stage, whose 192-B rows keep the transposed reads conflict-free; a 64-wide partial
-// takes its first 64 columns).  False if the shape does not qualify.
-bool marf_wgrad_l0_recompute_ok(int M, int ldz, int ldf0, long long S, int chunk, int n_chunks, long long Np_pad) {
-    return M == 256 && ldz % 8 == 0 && ldz >= M && (ldf0 == 96 || ldf0 == 64) && S % WG_SP0 == 0 && chunk % WG_SP0 == 0 &&
+// takes its first 64 columns).  False if the shape does not qualify.  L <= 16: the stage's 16
+// threads per row build two bands of one coordinate each, so bands 16..19 of L = 17..20 (whose
+// feat_0 is 96 wide too: columns 64..79) would stay unwritten; those nets store and read feat_0.
+bool marf_wgrad_l0_recompute_ok(int M, int ldz, int ldf0, int L, long long S, int chunk, int n_chunks,
+                                long long Np_pad) {
+    return M == 256 && ldz % 8 == 0 && ldz >= M && (ldf0 == 96 || ldf0 == 64) && L <= 16 && S % WG_SP0 == 0 &&
+           chunk % WG_SP0 == 0 &&
            (long long)n_chunks <= 0x7fffffff && Np_pad < (1 << 24) && (chunk + Np_pad - 1) / Np_pad + 1 <= F0_PATCHES;
 }
 
@@ -1195,6 +1199,7 @@ hipError_t marf_launch_wgrad_l0_recompute(const void* dz, int ldz, const GeoDev&
                                           float* bpartial, hipStream_t s, const WgRange* rng, int dtype) {
     WgArgs a;
     memset(&a, 0, sizeof(a));
+    if (L > 16 || (K0 != 96 && K0 != 64)) return hipErrorInvalidValue;  // (marf_wgrad_l0_recompute_ok)
     if (rng) {
         a.s_lo = rng->s_lo;
         a.s_len = rng->s_len;
@@ -1223,7 +1228,7 @@ hipError_t marf_launch_wgrad_l0_recompute(const void* dz, int ldz, const GeoDev&
 
 // ---- the fused launch: hidden layers in one launch, layer 0 beside it on `s2`, one reduction launch
 bool marf_wgrad_fused_ok(const WgFusedLayer* layers, int n_layers, long long S, int chunk, int n_chunks,
-                         long long Np_pad) {
+                         long long Np_pad, int L_bands) {
     if (!layers || n_layers < 1 || n_layers > WF_MAXJ || n_chunks < 1 || chunk < 64 || chunk % 64) return false;
     if (const char* e = getenv("MARF_WGRAD_FUSED")) {  // A/B switch (read per launch): 0 = per-layer launches
         if (e[0] == '0') return false;
@@ -1239,7 +1244,7 @@ bool marf_wgrad_fused_ok(const WgFusedLayer* layers, int n_layers, long long S, 
                     return false;
                 break;
             case 1:  // marf_launch_wgrad_l0_recompute's shape
-                if (!marf_wgrad_l0_recompute_ok(L.M, L.ldz, L.K, S, chunk, n_chunks, Np_pad)) return false;
+                if (!marf_wgrad_l0_recompute_ok(L.M, L.ldz, L.K, L_bands, S, chunk, n_chunks, Np_pad)) return false;
                 ++n_l0;
                 break;
             case 2:  // layer 0 stored: any shape marf_launch_wgrad takes (its kernel is picked there)

@@ -16,6 +16,8 @@ loss.all = 2 loss.rgb (use_edges off).  Switches:
            "dgrad_dzl" (W_h^T dz_l)
     acc    torch.float64 (default: the recipe's operand rounding alone) or torch.float32 (torch's own
            float32 summation order on top of it)
+    recipe "tile" (default), or "k_step2" / "k_step2dz": the pixel-per-wave kernel's dgrad (tests/step2_ref.py)
+    features, mutate: tests/step2_ref.py
 kink_pixels(inputs) names the pixels whose ReLU decisions depend on the accumulation order.
 The accumulators are float32 in the kernel, so every GEMM result is rounded to float32 here too.
 """
@@ -53,8 +55,24 @@ def mm3(a, b, acc, skip_a_lo=False, skip_b_lo=False):
     return r
 
 
-def step(cfg, params, warp, rgb, mask, progress, drop=(), acc=torch.float64, device="cpu"):
+def _dgrad_step2(dz, W, acc, drop, last, dz_lo):
+    """k_step2's dgrad GEMM (marf_step2.hip gemm MODE 2: A = W_h then W_l against one B): the last layer's
+    B holds g_h and g_l along k, so four terms; below it B is dz's one bf16 word, so two; k_step2dz's
+    hidden GEMMs (dz_lo) add W_h^T dz_l."""
+    r = _mm(dz[0], W[0], acc)
+    if "dgrad_wl" not in drop:
+        r = r + _mm(dz[0], W[1], acc)
+    if last or (dz_lo and "dgrad_dzl" not in drop):
+        r = r + _mm(dz[1], W[0], acc)
+    if last and "dgrad_wl" not in drop:
+        r = r + _mm(dz[1], W[1], acc)
+    return r
+
+
+def step(cfg, params, warp, rgb, mask, progress, drop=(), acc=torch.float64, device="cpu", recipe="tile", mutate=None,
+         features=None):
     f32 = torch.float32
+    assert recipe in ("tile", "k_step2", "k_step2dz"), recipe
     dev = torch.device(device)
 
     def T(a):
@@ -71,12 +89,14 @@ def step(cfg, params, warp, rgb, mask, progress, drop=(), acc=torch.float64, dev
     x = x.reshape(B * h * w, -1)
     Ws = [split(T(W)) for W, _ in params]
     bs = [T(b) for _, b in params]
-    # ---- forward
-    a = split(x.detach())
+    # ---- forward (features: the prologue's values from elsewhere, [pixels, 2 + 4L]; its adjoint stays torch's)
+    a = split(x.detach() if features is None else T(features).reshape(x.shape))
     acts, zs = [], []
     for l in range(n):
         # activations x weights^T: the "a" operand of mm3 is the activation pair, "b" the weight pair
         z = mm3(a, (Ws[l][0].t(), Ws[l][1].t()), acc, skip_a_lo="fwd_hl" in drop, skip_b_lo="fwd_lh" in drop)
+        if mutate is not None:  # (a defect put into the emulation: the mutation check of tests/step2_ref.py)
+            z = z + mutate(l, a, Ws[l]).to(z.dtype)
         z = (z + bs[l].to(acc)).to(f32)
         acts.append(a)
         zs.append(z)
@@ -97,7 +117,10 @@ def step(cfg, params, warp, rgb, mask, progress, drop=(), acc=torch.float64, dev
     for l in range(n - 1, -1, -1):
         if l < n - 1:
             grads[l] = (_mm(dz[0].t(), acts[l][0], acc).to(f32), dz[0].to(acc).sum(0).to(f32))
-        da = mm3(dz, Ws[l], acc, skip_a_lo="dgrad_dzl" in drop, skip_b_lo="dgrad_wl" in drop).to(f32)
+        if recipe == "tile":
+            da = mm3(dz, Ws[l], acc, skip_a_lo="dgrad_dzl" in drop, skip_b_lo="dgrad_wl" in drop).to(f32)
+        else:  # (the layer-0 adjoint reads dz_1's hi word in both k_step2 and k_step2dz)
+            da = _dgrad_step2(dz, Ws[l], acc, drop, l == n - 1, recipe == "k_step2dz" and l > 0).to(f32)
         if l > 0:
             dz = split(da * (zs[l - 1] > 0))
     x.backward(da)
