@@ -214,6 +214,28 @@ int marf_step_backward_ev(const marf_net* net, const marf_geometry* geo, const v
                           int lie_batch, const float* d_gout, const float* d_loss_out, float* d_dparams, float* d_dh,
                           void* const* layer_events, void* stream);
 
+/* ---- Warp-only fused step: register patches on a frozen image.  The reference keeps the neural
+ * image a module of its own "so it could be checkpointed" (model/planar.py:408); this is the use that
+ * anticipates: a trained image is loaded, its parameters do not move, and further patches (new views,
+ * a second batch, a re-registration after a bad start) are aligned to it.  marf_warp_step_forward is
+ * marf_step_forward with the same contract for d_rgb (may be NULL) and d_loss_out[3] and the same
+ * bits in both, on kernels that keep nothing for weight gradients: d_saved
+ * (marf_warp_step_saved_bytes) holds the dH partials (36 B per 32 pixel slots), the per-block loss
+ * partials and the band weights -- on the tile kernels also the ReLU records their own dgrad
+ * re-reads -- and no feat_l, dz_l, last-layer weight / bias partials or split-K partials.
+ * marf_warp_step_backward is the fixed-order sum of the dH partials and the Lie backward into d_dh
+ * [B][8] (the bits marf_step_backward gives), on the caller's stream alone: no side stream, no events.
+ * The pipelined mode (marf_net_set_pipeline) is ignored: there is no weight-gradient work to overlap.
+ * MARF_STEP2_GRID is honoured as by marf_step_forward.  MARF_FP16X2 nets and nets created under
+ * MARF_STEP2_DZ=1 or MARF_STEP2=1 have no warp-only kernel: MARF_ERR_UNSUPPORTED with the reason
+ * (marf_warp_step_saved_bytes returns 0 and sets it). */
+size_t marf_warp_step_saved_bytes(const marf_net* net, const marf_geometry* geo);
+int marf_warp_step_forward(const marf_net* net, const marf_geometry* geo, const marf_c2f* c2f, const void* d_packed,
+                           const float* d_gt, const float* d_mask, const float* d_denom_override, float* d_rgb,
+                           float* d_loss_out, void* d_saved, void* stream);
+int marf_warp_step_backward(const marf_net* net, const marf_geometry* geo, const void* d_saved, const float* d_h_params,
+                            int lie_batch, const float* d_gout, const float* d_loss_out, float* d_dh, void* stream);
+
 /* ---- MLP-gradient exchange of the patch-sharded step (the reference is
  * single-GPU, options.py:117-120, so this replaces no reference call: it is the one collective the
  * sharding adds).  RCCL over xGMI, librccl.so opened at first use.  marf_comm_unique_id fills 128

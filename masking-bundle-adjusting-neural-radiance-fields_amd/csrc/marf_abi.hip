@@ -1191,26 +1191,85 @@ static int wgrad_piece(const marf_net* net, const GeoDev& g, const Step2BufPlan&
     return MARF_OK;
 }
 
-static hipError_t launch_s2(const marf_net* n, const Step2Args& a, int grid, hipStream_t s) {
+// ---- the warp-only step (a frozen image: marf_warp_step_*)
+
+// why a net has no warp-only step (null: it has one)
+static const char* warp_step_refusal(const marf_net* n) {
+    if (n->dtype == MARF_FP16X2) return "precision fp16x2 (k_step2h) has no warp-only kernel; use bf16x3";
+    if (n->s2.variant >= 0 && n->s2.dz)
+        return "MARF_STEP2_DZ=1 (k_step2dz, the dgrad's dz split) has no warp-only kernel; create the net without it";
+    if (n->s2.variant == 0 || n->s2.variant == 2)
+        return "plain bf16 on the pixel-per-wave kernel (MARF_STEP2=1) has no warp-only kernel; create the net without it";
+    return nullptr;
+}
+
+// The warp-only step's buffer on the pixel-per-wave kernel: the dH partials (with the sink rows of a
+// group's missing second pixel set), the per-block loss partials, the lanes' sink for masked-off
+// stores and the band weights.  Nothing per pixel but the dH partials' 36 B per 32 slots.  The grid as
+// plan_step2_bufs chooses it (MARF_STEP2_GRID included), never pipelined.
+static void plan_warp2_bufs(const marf_net* n, const GeoDev& g, Step2BufPlan& p) {
+    const Step2NetPlan& q = n->s2;
+    memset(&p, 0, sizeof(p));
+    p.S = (long long)g.B * g.Np_pad;
+    p.n_tiles = (int)(p.S / q.TPX);
+    int cap = device_cus();
+    if (const char* e = getenv("MARF_STEP2_GRID")) cap = std::max(1, atoi(e));  // diagnostic override
+    p.grid = std::max(1, std::min(p.n_tiles, cap));
+    p.nblk = p.grid;
+    size_t off = 0;
+    p.dH = off;
+    off += rup((p.S + q.TPX) / q.PX * 9 * 4, 256);
+    p.loss = off;
+    off += rup((long long)p.nblk * 2 * 8, 256);
+    p.dummy = off;
+    off += rup((long long)p.grid * q.NW * 4096, 256);  // 64 B per lane
+    p.c2f = off;
+    off += 256;
+    p.total = off;
+}
+
+// The same on the tile kernels: the ReLU records (the kernel's own dgrad re-reads them), the per-tile
+// dH and loss partials and the band weights.
+static void plan_warp_tile(const marf_net* n, long long S, StepPlan& p) {
+    memset(&p, 0, sizeof(p));
+    size_t off = 0;
+    p.n_tiles = (int)(S / n->sTP);
+    for (int l = 1; l < n->n_layers; ++l) {
+        p.mask[l] = off;
+        off += rup(S / n->sTP * n->sNW * 1024, 256);  // one uint4 per lane per wave per tile
+    }
+    p.dH = off;
+    off += rup((long long)p.n_tiles * 9 * 4, 256);
+    p.loss = off;
+    off += rup((long long)p.n_tiles * 2 * 8, 256);
+    p.c2f = off;
+    off += 256;
+    p.total = off;
+}
+
+static hipError_t launch_s2(const marf_net* n, const Step2Args& a, int grid, hipStream_t s, bool warp = false) {
     const Step2NetPlan& q = n->s2;
     // the compile-time layer-0 instantiations: split recipe, every hidden layer 256 wide, the
     // layer-0 row tiles per stage the kernel derives from nk0, a 256-wide last-layer input
     bool full = (q.variant == 1 || q.variant == 3) && q.nk0 >= 1 && q.r0 == std::max(1, std::min(8, 16 / q.nk0)) && q.Kl == 256;
     for (int l = 0; l < n->n_layers - 1; ++l) full = full && n->Mp[l] == 256;
     if (const char* e = getenv("MARF_STEP2_GENERIC")) full = full && e[0] != '1';  // (A/B: the generic kernel)
+    if (warp) return marf_launch_step2_warp(a, grid, s, full ? q.nk0 : 0);
     return marf_launch_step2(a, q.variant, grid, s, full ? q.nk0 : 0, q.dz);
 }
 
 static int step2_forward(const marf_net* net, const marf_geometry* geo, const marf_c2f* c2f, const void* d_packed,
                          const float* d_gt, const float* d_mask, const float* d_denom_override, float* d_rgb,
-                         float* d_loss_out, void* d_saved, hipStream_t s, bool render = false) {
+                         float* d_loss_out, void* d_saved, hipStream_t s, bool render = false, bool warp = false) {
+    // warp: the warp-only step (k_step2w on plan_warp2_bufs): no saved tensor, no wlast / blast
     const Step2NetPlan& q = net->s2;
     Step2Args a;
     memset(&a, 0, sizeof(a));
     int rc = make_geo(geo, a.geo, q.TPX);
     if (rc) return rc;
     Step2BufPlan p;
-    plan_step2_bufs(net, a.geo, p, render);
+    if (warp) plan_warp2_bufs(net, a.geo, p);
+    else plan_step2_bufs(net, a.geo, p, render);
     char* sv = (char*)d_saved;
     const char* pk = (const char*)d_packed;
     const int nl = net->n_layers;
@@ -1233,7 +1292,7 @@ static int step2_forward(const marf_net* net, const marf_geometry* geo, const ma
     }
     a.bias = (const float*)(pk + q.bias_off);
     a.nbias = q.nbias;
-    a.feat0_recompute = !render && l0_recompute(net, a.geo, p.S) ? 1 : 0;
+    a.feat0_recompute = !render && !warp && l0_recompute(net, a.geo, p.S) ? 1 : 0;
     if (p.dzl) {
         a.dzl_g = sv + p.dzl_g;
         a.dzl_mk = sv + p.dzl_mk;
@@ -1249,13 +1308,13 @@ static int step2_forward(const marf_net* net, const marf_geometry* geo, const ma
         y.boff = q.boff[l];
         y.ldf = l == 0 ? q.ldf0 : net->Kp[l];
         y.ldz = net->Kp[l];
-        y.feat = l < nl - 1 && !render ? (u16*)(sv + p.feat[l]) : nullptr;
-        y.dz = l >= 1 && !render && !(p.dzl && l == nl - 1) ? (u16*)(sv + p.dz[l]) : nullptr;
+        y.feat = l < nl - 1 && !render && !warp ? (u16*)(sv + p.feat[l]) : nullptr;
+        y.dz = l >= 1 && !render && !warp && !(p.dzl && l == nl - 1) ? (u16*)(sv + p.dz[l]) : nullptr;
     }
     a.dH_partial = (float*)(sv + p.dH);
     a.loss_partial = (double*)(sv + p.loss);
-    a.blast_partial = (float*)(sv + p.blast);
-    a.wlast_partial = (float*)(sv + p.wlast);
+    a.blast_partial = warp ? nullptr : (float*)(sv + p.blast);
+    a.wlast_partial = warp ? nullptr : (float*)(sv + p.wlast);
     a.Kl = q.Kl;
     a.c2f_w = (const float*)(sv + p.c2f);
     a.dummy = (float*)(sv + p.dummy);
@@ -1280,6 +1339,16 @@ static int step2_forward(const marf_net* net, const marf_geometry* geo, const ma
     a.lds_total = off;
     if (off > 160 * 1024) return fail(MARF_ERR_UNSUPPORTED, "step2: LDS plan %d B exceeds 160 KB", off);
     // the band weights and the layer-0 column map (packed buffer -> saved buffer) in one launch
+    if (warp) {  // (no weight gradient reads the layer-0 column map)
+        HIPCHK(marf_launch_c2f_weights(cf, net->L, (float*)(sv + p.c2f), s), "warp_step_forward c2f");
+        {
+            MarfProfScope ps("mlp_step_warp", s);
+            HIPCHK(launch_s2(net, a, p.grid, s, true), "warp_step_forward step2");
+        }
+        MarfProfScope ps("loss_final", s);
+        HIPCHK(marf_launch_loss_final(a.loss_partial, p.nblk, d_loss_out, d_denom_override, s), "warp_step_forward loss");
+        return MARF_OK;
+    }
     HIPCHK(marf_launch_c2f_weights(cf, net->L, (float*)(sv + p.c2f), s, (const int*)(pk + q.kmap_off),
                                    (int*)(sv + p.kmap), net->D),
            "step_forward c2f / kmap");
@@ -1554,14 +1623,12 @@ size_t marf_step_saved_bytes(const marf_net* net, const marf_geometry* geo) {
     return p.total;
 }
 
-int marf_step_forward(const marf_net* net, const marf_geometry* geo, const marf_c2f* c2f, const void* d_packed,
-                      const float* d_gt, const float* d_mask, const float* d_denom_override, float* d_rgb,
-                      float* d_loss_out, void* d_saved, void* stream) {
-    if (!net || !d_packed || !d_gt || !d_loss_out || !d_saved) return fail(MARF_ERR_INVALID, "step_forward: NULL argument");
-    if (!geo || geo->mode == MARF_GEO_COORDS) return fail(MARF_ERR_INVALID, "step_forward: needs a pixel-grid geometry");
-    hipStream_t s = (hipStream_t)stream;
-    if (use_step2(net))
-        return step2_forward(net, geo, c2f, d_packed, d_gt, d_mask, d_denom_override, d_rgb, d_loss_out, d_saved, s);
+// The tile kernels' fused step forward (k_mlp_step / k_mlp_step_split), full or warp-only: one geometry, one
+// argument set-up and one launch sequence.  The warp-only step differs in its plan (ReLU records, dH and loss
+// partials, the c2f table: nothing for a weight gradient), in the instantiation and in its profile name.
+static int tile_step_forward(const marf_net* net, const marf_geometry* geo, const marf_c2f* c2f, const void* d_packed,
+                             const float* d_gt, const float* d_mask, const float* d_denom_override, float* d_rgb,
+                             float* d_loss_out, void* d_saved, hipStream_t s, bool warp) {
     StepArgs a;
     memset(&a, 0, sizeof(a));
     int rc = make_geo(geo, a.geo, MARF_TILE_PAD);
@@ -1574,33 +1641,52 @@ int marf_step_forward(const marf_net* net, const marf_geometry* geo, const marf_
     a.S = (long long)a.geo.B * a.geo.Np_pad;
     a.lda = net->lda;
     StepPlan p;
-    plan_step(net, a.S, p);
+    if (warp)
+        plan_warp_tile(net, a.S, p);
+    else
+        plan_step(net, a.S, p);
     char* sv = (char*)d_saved;
     const int nl = net->n_layers;
-    for (int l = 0; l < nl - 1; ++l) a.feat[l] = sv + p.feat[l];
-    for (int l = 1; l < nl; ++l) {
-        a.dz[l] = sv + p.dz[l];
-        a.mask_bits[l] = (uint64_t*)(sv + p.mask[l]);
+    for (int l = 1; l < nl; ++l) a.mask_bits[l] = (uint64_t*)(sv + p.mask[l]);
+    if (!warp) {  // (the warp-only plan has no feat / dz / wlast / blast)
+        for (int l = 0; l < nl - 1; ++l) a.feat[l] = sv + p.feat[l];
+        for (int l = 1; l < nl; ++l) a.dz[l] = sv + p.dz[l];
+        a.wlast_partial = (float*)(sv + p.wlast);
+        a.blast_partial = (float*)(sv + p.blast);
     }
-    a.wlast_partial = (float*)(sv + p.wlast);
-    a.blast_partial = (float*)(sv + p.blast);
     a.dH_partial = (float*)(sv + p.dH);
     a.loss_partial = (double*)(sv + p.loss);
     a.c2f_w = (const float*)(sv + p.c2f);
     a.stamps = g_stamps;
-    if (net->L > 0) HIPCHK(marf_launch_c2f_weights(a.c2f, net->L, (float*)(sv + p.c2f), s), "step_forward c2f");
+    if (net->L > 0)
+        HIPCHK(marf_launch_c2f_weights(a.c2f, net->L, (float*)(sv + p.c2f), s),
+               warp ? "warp_step_forward c2f" : "step_forward c2f");
     {
-        MarfProfScope ps("mlp_step", s);
+        MarfProfScope ps(warp ? "mlp_step_warp" : "mlp_step", s);
         if (net->tsplit)
-            HIPCHK(marf_launch_mlp_step_split(a, net->sTP, false, net->lds_step, p.n_tiles, s), "step_forward split");
+            HIPCHK(marf_launch_mlp_step_split(a, net->sTP, false, net->lds_step, p.n_tiles, s, warp),
+                   warp ? "warp_step_forward split" : "step_forward split");
         else
-            HIPCHK(marf_launch_mlp_step(a, net->kdt, net->sTP, net->sNW, net->lds_step, p.n_tiles, s), "step_forward");
+            HIPCHK(marf_launch_mlp_step(a, net->kdt, net->sTP, net->sNW, net->lds_step, p.n_tiles, s, warp),
+                   warp ? "warp_step_forward" : "step_forward");
     }
     {
         MarfProfScope ps("loss_final", s);
-        HIPCHK(marf_launch_loss_final(a.loss_partial, p.n_tiles, d_loss_out, d_denom_override, s), "step_forward loss");
+        HIPCHK(marf_launch_loss_final(a.loss_partial, p.n_tiles, d_loss_out, d_denom_override, s),
+               warp ? "warp_step_forward loss" : "step_forward loss");
     }
     return MARF_OK;
+}
+
+int marf_step_forward(const marf_net* net, const marf_geometry* geo, const marf_c2f* c2f, const void* d_packed,
+                      const float* d_gt, const float* d_mask, const float* d_denom_override, float* d_rgb,
+                      float* d_loss_out, void* d_saved, void* stream) {
+    if (!net || !d_packed || !d_gt || !d_loss_out || !d_saved) return fail(MARF_ERR_INVALID, "step_forward: NULL argument");
+    if (!geo || geo->mode == MARF_GEO_COORDS) return fail(MARF_ERR_INVALID, "step_forward: needs a pixel-grid geometry");
+    hipStream_t s = (hipStream_t)stream;
+    if (use_step2(net))
+        return step2_forward(net, geo, c2f, d_packed, d_gt, d_mask, d_denom_override, d_rgb, d_loss_out, d_saved, s);
+    return tile_step_forward(net, geo, c2f, d_packed, d_gt, d_mask, d_denom_override, d_rgb, d_loss_out, d_saved, s, false);
 }
 
 int marf_step_backward(const marf_net* net, const marf_geometry* geo, const void* d_saved, const float* d_h_params,
@@ -1666,6 +1752,75 @@ int marf_step_backward_ev(const marf_net* net, const marf_geometry* geo, const v
                                      lie_batch > 0 ? lie_batch : g.B, s, d_gout, denom),
                "step_backward warp");
     }
+    return MARF_OK;
+}
+
+// ---- the warp-only step: a frozen image registers further patches (include/marf.h)
+
+size_t marf_warp_step_saved_bytes(const marf_net* net, const marf_geometry* geo) {
+    GeoDev g;
+    if (!net || !geo || geo->mode == MARF_GEO_COORDS) return 0;
+    if (const char* why = warp_step_refusal(net)) {
+        fail(MARF_ERR_UNSUPPORTED, "warp_step: %s", why);
+        return 0;
+    }
+    if (use_step2(net)) {
+        if (make_geo(geo, g, net->s2.TPX) != MARF_OK) return 0;
+        Step2BufPlan p2;
+        plan_warp2_bufs(net, g, p2);
+        return p2.total;
+    }
+    if (make_geo(geo, g, MARF_TILE_PAD) != MARF_OK) return 0;
+    StepPlan p;
+    plan_warp_tile(net, (long long)g.B * g.Np_pad, p);
+    return p.total;
+}
+
+int marf_warp_step_forward(const marf_net* net, const marf_geometry* geo, const marf_c2f* c2f, const void* d_packed,
+                           const float* d_gt, const float* d_mask, const float* d_denom_override, float* d_rgb,
+                           float* d_loss_out, void* d_saved, void* stream) {
+    if (!net || !d_packed || !d_gt || !d_loss_out || !d_saved) return fail(MARF_ERR_INVALID, "warp_step_forward: NULL argument");
+    if (!geo || geo->mode == MARF_GEO_COORDS) return fail(MARF_ERR_INVALID, "warp_step_forward: needs a pixel-grid geometry");
+    if (const char* why = warp_step_refusal(net)) return fail(MARF_ERR_UNSUPPORTED, "warp_step_forward: %s", why);
+    hipStream_t s = (hipStream_t)stream;
+    if (use_step2(net))
+        return step2_forward(net, geo, c2f, d_packed, d_gt, d_mask, d_denom_override, d_rgb, d_loss_out, d_saved, s, false,
+                             true);
+    return tile_step_forward(net, geo, c2f, d_packed, d_gt, d_mask, d_denom_override, d_rgb, d_loss_out, d_saved, s, true);
+}
+
+// the fixed-order sum of the dH partials and the Lie backward, on the caller's stream alone
+int marf_warp_step_backward(const marf_net* net, const marf_geometry* geo, const void* d_saved, const float* d_h_params,
+                            int lie_batch, const float* d_gout, const float* d_loss_out, float* d_dh, void* stream) {
+    if (!net || !d_saved || !d_gout || !d_loss_out || !d_dh || !d_h_params)
+        return fail(MARF_ERR_INVALID, "warp_step_backward: NULL argument");
+    if (!geo || geo->mode == MARF_GEO_COORDS) return fail(MARF_ERR_INVALID, "warp_step_backward: needs a pixel-grid geometry");
+    if (const char* why = warp_step_refusal(net)) return fail(MARF_ERR_UNSUPPORTED, "warp_step_backward: %s", why);
+    hipStream_t s = (hipStream_t)stream;
+    const char* sv = (const char*)d_saved;
+    const float* denom = d_loss_out + 1;
+    GeoDev g;
+    size_t dH;
+    int per_patch;
+    if (use_step2(net)) {
+        int rc = make_geo(geo, g, net->s2.TPX);
+        if (rc) return rc;
+        Step2BufPlan p;
+        plan_warp2_bufs(net, g, p);
+        dH = p.dH;
+        per_patch = g.Np_pad / net->s2.PX;
+    } else {
+        int rc = make_geo(geo, g, MARF_TILE_PAD);
+        if (rc) return rc;
+        StepPlan p;
+        plan_warp_tile(net, (long long)g.B * g.Np_pad, p);
+        dH = p.dH;
+        per_patch = g.Np_pad / net->sTP;
+    }
+    MarfProfScope ps("warp_bwd", s);
+    HIPCHK(marf_launch_reduce_dH((const float*)(sv + dH), per_patch, g.B, d_h_params, nullptr, d_dh,
+                                 lie_batch > 0 ? lie_batch : g.B, s, d_gout, denom),
+           "warp_step_backward warp");
     return MARF_OK;
 }
 

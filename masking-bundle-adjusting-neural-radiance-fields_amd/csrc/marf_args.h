@@ -252,14 +252,19 @@ hipError_t marf_launch_mask_fwd(const marf::MaskFwdArgs& a, size_t lds, int n_ti
 hipError_t marf_launch_mask_bwd(const marf::MaskBwdArgs& a, size_t lds, int n_tiles, hipStream_t s);
 hipError_t marf_launch_mse_mask_bwd(const float* pred, const float* gt, const float* mask, int B, int Np,
                                     const float* stats, const float* gout, float* d_mask, hipStream_t s);
-hipError_t marf_launch_mlp_step(const marf::StepArgs& a, int dtype, int TP, int NW, size_t lds, int n_tiles, hipStream_t s);
+// warp_only (both tile steps): the frozen-image instantiations -- nothing saved for weight gradients,
+// no last-layer weight / bias gradient partials (feat / dz / wlast_partial / blast_partial unused)
+hipError_t marf_launch_mlp_step(const marf::StepArgs& a, int dtype, int TP, int NW, size_t lds, int n_tiles, hipStream_t s,
+                                bool warp_only = false);
 // the split tile step of MARF_BF16X3 nets beyond k_step2's reach (marf_step_split.hip); TP 64 or 128
 hipError_t marf_launch_mlp_step_split(const marf::StepArgs& a, int TP, bool fwd_only, size_t lds, int n_tiles,
-                                      hipStream_t s);
+                                      hipStream_t s, bool warp_only = false);
 hipError_t marf_launch_c2f_weights(const marf::C2fDev& c, int L, float* out, hipStream_t s,
                                    const int* csrc = nullptr, int* cdst = nullptr, int cn = 0);
 hipError_t marf_launch_loss_final(const double* part, int n, float* out, const float* denom_override, hipStream_t s);
 hipError_t marf_launch_step2(const marf::Step2Args& a, int variant, int grid, hipStream_t s, int full_nk0, bool dz = false);
+// the warp-only step (k_step2w: the bf16 split recipe with nothing saved; marf_warp_step_forward)
+hipError_t marf_launch_step2_warp(const marf::Step2Args& a, int grid, hipStream_t s, int full_nk0);
 hipError_t marf_launch_pack2(const float* params, void* prog, float* bias_out, int* kmap, const marf::Pack2Args& a,
                              hipStream_t s);
 hipError_t marf_launch_edge_map(const float* in, double* out, int n_img, int H, int W, hipStream_t s);

@@ -1083,8 +1083,9 @@ MARF_DEV void step_loss_slots(const StepArgs& a, const f32x4 (&acc)[NJ], int wav
     }
 }
 
-// Masked-MSE partial of the tile (fp64, fixed order; wave 0) and the last bias gradient (wave 1).
-template <int TP>
+// Masked-MSE partial of the tile (fp64, fixed order; wave 0) and the last bias gradient (wave 1;
+// BLAST = false: the warp-only step has no bias gradient).
+template <int TP, bool BLAST = true>
 MARF_DEV void step_tile_partials(const StepArgs& a, int wave, int lane, const float (&gl)[TP][4],
                                  const float (&lsum)[2][TP]) {
     if (wave == 0) {
@@ -1099,7 +1100,7 @@ MARF_DEV void step_tile_partials(const StepArgs& a, int wave, int lane, const fl
             a.loss_partial[2 * (size_t)blockIdx.x] = s0;
             a.loss_partial[2 * (size_t)blockIdx.x + 1] = s1;
         }
-    } else if (wave == 1) {
+    } else if (BLAST && wave == 1) {
         float s[3] = {0.f, 0.f, 0.f};
         for (int px = lane; px < TP; px += 64)
 #pragma unroll

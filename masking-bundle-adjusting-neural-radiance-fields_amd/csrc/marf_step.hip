@@ -40,7 +40,10 @@ constexpr int MARF_STEP_NBIAS = 1024;
 // pixel tiles' MFMAs instead of 2 -- half the weight-fragment traffic per MFMA of TP = 64)
 // SK: the net has skip layers (their prologue / posenc-gradient code is compiled in only then: it
 // costs the plain nets registers and spills)
-template <class P, int TP, bool BL, int NW, bool SK>
+// WO: warp-only (a frozen image, marf_warp_step_forward): no tile is queued for saving (the view's
+// store stays cleared, so no GEMM flushes one), no last-layer weight / bias gradient partials; the
+// ReLU records stay (this kernel's own dgrad re-reads them)
+template <class P, int TP, bool BL, int NW, bool SK, bool WO = false>
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void k_mlp_step(StepArgs a) {
     typedef typename P::T T;
     constexpr int PT = TP / 32;
@@ -85,7 +88,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void k_mlp_step(StepArgs 
     __syncthreads();
     STAMP(1);
     // every saved tile streams out during the GEMM that reads it next (TileStore)
-    v.template queue_save<NW>(a.feat[0], slot0, 0, TP, net.Kp[0], MARF_DIAG_SAVE(net));
+    if constexpr (!WO) v.template queue_save<NW>(a.feat[0], slot0, 0, TP, net.Kp[0], MARF_DIAG_SAVE(net));
 
     // ---- hidden layers (forward); the last one is peeled so the last layer's weight fragments
     //      can be in flight behind its epilogue without pinning registers through the loop
@@ -109,7 +112,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void k_mlp_step(StepArgs 
             __syncthreads();
         }
         v.clear_save();
-        if (l + 1 < nl - 1) {  // the last layer's input never leaves LDS
+        if (!WO && l + 1 < nl - 1) {  // the last layer's input never leaves LDS
             const int Kn = net.Kp[l + 1];  // (M + Kp0 for a skip layer)
             v.template queue_save<NW>(a.feat[l + 1], slot0, 0, TP, Kn, MARF_DIAG_SAVE(net));
         }
@@ -168,8 +171,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void k_mlp_step(StepArgs 
     __syncthreads();
 
     STAMP(9);
-    step_tile_partials<TP>(a, wave, lane, gl, lsum);
-    step_wlast_grad<P, TP, NW>(a, Kl, v.feat(), v.lda, wave, lane, gT);
+    step_tile_partials<TP, !WO>(a, wave, lane, gl, lsum);
+    if constexpr (!WO) step_wlast_grad<P, TP, NW>(a, Kl, v.feat(), v.lda, wave, lane, gT);
     __syncthreads();  // feat_{n-1} consumed
 
     step_fill_d<TP>(v, gl, net.Mt[nl - 1], net.diag[nl - 1]);
@@ -192,7 +195,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void k_mlp_step(StepArgs 
         dgrad_epilogue<RT, PT, NW>(acc, net, l, v, wave, lane, mw, dsk);
         __syncthreads();
         if (l <= 4) STAMP(15 - l);  // 14 .. 11
-        v.template queue_save<NW>(a.dz[l], slot0, 0, TP, R, MARF_DIAG_SAVE(net));
+        if constexpr (!WO) v.template queue_save<NW>(a.dz[l], slot0, 0, TP, R, MARF_DIAG_SAVE(net));
     }
 
     // ---- layer-0 dgrad + posenc / warp adjoint -> dH partial
@@ -250,43 +253,51 @@ __global__ __launch_bounds__(256) void k_loss_final(const double* __restrict__ p
 
 using namespace marf;
 
-template <class P, int TP, bool BL, int NW, bool SK>
+template <class P, int TP, bool BL, int NW, bool SK, bool WO>
 static hipError_t launch_step_sk(const StepArgs& a, size_t lds, int n_tiles, hipStream_t s) {
     {
-        hipError_t e = ensure_dynamic_lds((const void*)k_mlp_step<P, TP, BL, NW, SK>, lds);
+        hipError_t e = ensure_dynamic_lds((const void*)k_mlp_step<P, TP, BL, NW, SK, WO>, lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL((k_mlp_step<P, TP, BL, NW, SK>), dim3(n_tiles), dim3(64 * NW), lds, s, a);
+    hipLaunchKernelGGL((k_mlp_step<P, TP, BL, NW, SK, WO>), dim3(n_tiles), dim3(64 * NW), lds, s, a);
     return hipGetLastError();
 }
 
-template <class P, int TP, bool BL, int NW>
+template <class P, int TP, bool BL, int NW, bool WO>
 static hipError_t launch_step_t(const StepArgs& a, size_t lds, int n_tiles, hipStream_t s) {
-    return a.net.skip ? launch_step_sk<P, TP, BL, NW, true>(a, lds, n_tiles, s)
-                      : launch_step_sk<P, TP, BL, NW, false>(a, lds, n_tiles, s);
+    return a.net.skip ? launch_step_sk<P, TP, BL, NW, true, WO>(a, lds, n_tiles, s)
+                      : launch_step_sk<P, TP, BL, NW, false, WO>(a, lds, n_tiles, s);
 }
 
-template <class P, int TP, int NW>
+template <class P, int TP, int NW, bool WO>
 static hipError_t launch_step_b(const StepArgs& a, size_t lds, int n_tiles, hipStream_t s) {
     int nb = 0;
     for (int l = 0; l + 1 < a.net.n_layers; ++l) nb += a.net.Mp[l];
-    if (nb <= MARF_STEP_NBIAS) return launch_step_t<P, TP, true, NW>(a, lds, n_tiles, s);
-    return launch_step_t<P, TP, false, NW>(a, lds, n_tiles, s);
+    if (nb <= MARF_STEP_NBIAS) return launch_step_t<P, TP, true, NW, WO>(a, lds, n_tiles, s);
+    return launch_step_t<P, TP, false, NW, WO>(a, lds, n_tiles, s);
 }
 
-template <class P>
+template <class P, bool WO>
 static hipError_t launch_step_p(const StepArgs& a, int TP, int NW, size_t lds, int n_tiles, hipStream_t s) {
-    if (TP == 128 && NW == 8) return launch_step_b<P, 128, 8>(a, lds, n_tiles, s);
+    if (TP == 128 && NW == 8) return launch_step_b<P, 128, 8, WO>(a, lds, n_tiles, s);
     if (NW != 4) return hipErrorInvalidValue;
-    return TP == 128 ? launch_step_b<P, 128, 4>(a, lds, n_tiles, s) : launch_step_b<P, 64, 4>(a, lds, n_tiles, s);
+    return TP == 128 ? launch_step_b<P, 128, 4, WO>(a, lds, n_tiles, s) : launch_step_b<P, 64, 4, WO>(a, lds, n_tiles, s);
 }
 
-// TP pixel slots per block tile, NW waves per block (4, or 8 for the 16-bit recipes at TP = 128)
-hipError_t marf_launch_mlp_step(const StepArgs& a, int dtype, int TP, int NW, size_t lds, int n_tiles, hipStream_t s) {
-    if (dtype == 1) return launch_step_p<PrecBF16>(a, TP, NW, lds, n_tiles, s);
-    if (dtype == 2) return launch_step_p<PrecF16>(a, TP, NW, lds, n_tiles, s);
+template <bool WO>
+static hipError_t launch_step_d(const StepArgs& a, int dtype, int TP, int NW, size_t lds, int n_tiles, hipStream_t s) {
+    if (dtype == 1) return launch_step_p<PrecBF16, WO>(a, TP, NW, lds, n_tiles, s);
+    if (dtype == 2) return launch_step_p<PrecF16, WO>(a, TP, NW, lds, n_tiles, s);
     if (NW != 4) return hipErrorInvalidValue;
-    return TP == 128 ? launch_step_b<PrecF32, 128, 4>(a, lds, n_tiles, s) : launch_step_b<PrecF32, 64, 4>(a, lds, n_tiles, s);
+    return TP == 128 ? launch_step_b<PrecF32, 128, 4, WO>(a, lds, n_tiles, s) : launch_step_b<PrecF32, 64, 4, WO>(a, lds, n_tiles, s);
+}
+
+// TP pixel slots per block tile, NW waves per block (4, or 8 for the 16-bit recipes at TP = 128);
+// warp_only: k_mlp_step's WO instantiations
+hipError_t marf_launch_mlp_step(const StepArgs& a, int dtype, int TP, int NW, size_t lds, int n_tiles, hipStream_t s,
+                                bool warp_only) {
+    return warp_only ? launch_step_d<true>(a, dtype, TP, NW, lds, n_tiles, s)
+                     : launch_step_d<false>(a, dtype, TP, NW, lds, n_tiles, s);
 }
 
 hipError_t marf_launch_c2f_weights(const C2fDev& c, int L, float* out, hipStream_t s, const int* csrc, int* cdst,

@@ -144,7 +144,12 @@ struct S2Cfg {
 // exact 2^10 gradient scale; the saved tensors are fp16 and the weight gradients run in fp16
 // (marf_wgrad.hip PrecF16, the 2^-10 in the reduction).  Compile-time layer-0 instantiations only
 // (full-width nets).
-template <int HM, bool SPLIT, int NW, int MAXR, int NK0F, int NTAF, bool DZ, bool HF = false>
+// WO (warp-only: the image is frozen, marf_warp_step_forward): the same forward, loss, dgrad chain,
+// adjoint and dH partials with nothing kept for weight gradients -- no feat_l / dz_l / feat_0 / dzl_*
+// stores, no last-layer weight gradient (its LDS transpose and wla image) and no wlast / blast
+// partials.  Every store that remains (rgb, the dH partials) still counts itself in st_cur, so the
+// ring waits stay exact.  The bf16 split recipe only (not DZ, not HF).
+template <int HM, bool SPLIT, int NW, int MAXR, int NK0F, int NTAF, bool DZ, bool HF = false, bool WO = false>
 __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Args& a) {
     typedef S2Cfg<HM, SPLIT, NW, MAXR, DZ> C;
     constexpr bool SDZ = SPLIT && DZ;
@@ -152,6 +157,7 @@ __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Ar
     constexpr bool FIX = NK0F > 0;
     static_assert(NK0F <= C::NK0, "layer-0 k-steps");
     static_assert(!HF || (SPLIT && !DZ && NK0F > 0 && NS == 2), "fp16x2: split dgrad, two sets, compile-time layer 0");
+    static_assert(!WO || (SPLIT && !DZ && !HF), "warp-only: the bf16 split recipe");
     // the hidden dgrad of a group's two pixel sets in one pass per weight stage (compile-time nets;
     // MARF_STEP2_J2=0 at build time keeps one pass per set for A/B)
 #ifndef MARF_STEP2_J2
@@ -163,7 +169,7 @@ __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Ar
     constexpr float kGS = 1024.f;
     // dz_{n-1} may be left to the weight gradient (Step2Args::dzl_g): the bf16 split recipe with a
     // bf16 dz; k_step2dz and k_step2h keep the saved path (the host never sets dzl_g for them)
-    constexpr bool DZL_OK = SPLIT && !DZ && !HF && C::NMW == 4;
+    constexpr bool DZL_OK = SPLIT && !DZ && !HF && !WO && C::NMW == 4;
     constexpr int R0Q = NKH / (FIX ? NK0F : NKH);  // layer-0 row tiles per stage (the host's r0)
     constexpr int R0F = R0Q < 1 ? 1 : (R0Q > NRT ? NRT : R0Q);
     // one wave per SIMD (512 registers): the B operand arrays live in the accumulator half (s2_park)
@@ -204,8 +210,10 @@ __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Ar
     if ((int)threadIdx.x < 32) c2f_l[threadIdx.x] = (int)threadIdx.x < L ? a.c2f_w[threadIdx.x] : 0.f;
     for (int e = threadIdx.x; e < nl * LYW; e += NW * 64)
         lyr[e] = ld_as<uint32_t>(reinterpret_cast<const char*>(a.layers) + 4 * e);
-    for (int e = lane; e < 512; e += 64) st_as<uint32_t>(gts + 2 * e, 0u);
-    for (int e = lane; e < 3 * a.Kl; e += 64) wla[e] = 0.f;
+    if constexpr (!WO) {  // (the last-layer weight gradient's g^T image and its accumulators)
+        for (int e = lane; e < 512; e += 64) st_as<uint32_t>(gts + 2 * e, 0u);
+        for (int e = lane; e < 3 * a.Kl; e += 64) wla[e] = 0.f;
+    }
     if constexpr (DZL_OK) {
         // the last-layer dgrad stage's row tiles (hi, then lo) for the weight gradient that recomputes
         // dz_{n-1}: the backward has no packed buffer at hand
@@ -678,7 +686,9 @@ __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Ar
         } else {
             mks[(l * C::NMW + (rt >> 1)) * 64 + lane] = mpend | ep.bits;
         }
-        if (save) store_rt(srow, rtc, Oh[2 * rt], Oh[2 * rt + 1]);
+        if constexpr (!WO) {
+            if (save) store_rt(srow, rtc, Oh[2 * rt], Oh[2 * rt + 1]);
+        }
     };
     // dgrad step e: dz = acc * relu'(z) with the mask word e.mw
     auto bstep = [&](EpSt& es, const f32x16& pa, auto ec, auto rtc) {
@@ -725,7 +735,9 @@ __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Ar
             Ol[2 * rt].u = make_uint4(es.lw[0], es.lw[1], es.lw[2], es.lw[3]);
             Ol[2 * rt + 1].u = make_uint4(es.lw[4], es.lw[5], es.lw[6], es.lw[7]);
         }
-        if (save) store_rt(row0, rtc, O[2 * rt], O[2 * rt + 1]);
+        if constexpr (!WO) {
+            if (save) store_rt(row0, rtc, O[2 * rt], O[2 * rt + 1]);
+        }
     };
     // ---- the fp16x2 forward (HF): helpers
     // one 32-row output tile of BOTH pixel sets: c_s += A_hi . B_s + A_lo . B_s over NK k-steps (fp16
@@ -1293,7 +1305,7 @@ __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Ar
                 // feat_0 (bf16 hi) for the layer-0 weight gradient: column 16 ks + 8 h + j
                 // (every armed DMA piece was issued before the previous store: these count as the
                 //  current stage's stores)
-                if (!a.fwd_only && !a.feat0_recompute) {  // (T16: k-step g = feature block g)
+                if (!WO && !a.fwd_only && !a.feat0_recompute) {  // (T16: k-step g = feature block g)
                     u16* row = ly_ptr(0, 0) + (slot0 >> 5) * ly_int(0, 3) * 32 + pxl * 16 + 8 * h;
 #pragma unroll
                     for (int g = 0; g < C::NK0; ++g)
@@ -1316,7 +1328,7 @@ __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Ar
                 typedef std::integral_constant<bool, decltype(nk_tag)::value == NKH> PcL;  // hidden: pieces in the GEMM
                 constexpr bool SPLITPK = SPLIT && MS == 1 && decltype(nk_tag)::value == NKH;  // hidden, split recipe
                 const int nrt = FIX ? NRT : ly_int(l, 0);
-                const bool save = l + 1 < nl - 1 && !a.fwd_only;
+                const bool save = !WO && l + 1 < nl - 1 && !a.fwd_only;
                 u16* srow = save ? ly_ptr(l + 1, 0) + (slot0 >> 5) * ly_int(l + 1, 3) * 32 + pxl * 16 + 8 * h : nullptr;
                 const int boff = ly_int(l, 2);
                 const char* slot0 = nullptr;
@@ -1464,7 +1476,7 @@ __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Ar
             // ---- last-layer weight gradient of the wave's 32 pixels: dW[c][k] += sum_px g[c] feat[k]
             //      16x16x32 MFMA: A = g^T (rows 0-2 hi, 4-6 lo; K = 32 pixels) from a wave-private
             //      LDS image, B = feat^T per 16-feature k-step through a transposing LDS round trip
-            {
+            if constexpr (!WO) {
                 if (h == 0) {
                     const uint32_t w0 = Bg.u.x, w1 = Bg.u.y, w2 = Bg.u.z, w3 = Bg.u.w;
                     gts[0 * 32 + pxl] = (u16)(w0 & 0xffff);
@@ -1568,7 +1580,7 @@ __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Ar
             // dz_{n-1} recomputed by the weight gradient of layer n-2: instead of its row tiles, each
             // set's g fragment (lane half 0) and its lanes' mask words of this layer -- two 16-B lane
             // stores per set (marf_args.h DZL_G_SET ..)
-            bool save_dz = true;
+            bool save_dz = !WO;
             if constexpr (DZL_OK) {
                 if (a.dzl_g) {
                     save_dz = false;
@@ -1893,13 +1905,15 @@ __device__ __attribute__((always_inline)) inline void k_step2_body(const Step2Ar
             sf += (float)red[w * 5 + threadIdx.x];
         }
         if (threadIdx.x < 2) a.loss_partial[2 * (size_t)blockIdx.x + threadIdx.x] = s;
-        else a.blast_partial[3 * (size_t)blockIdx.x + threadIdx.x - 2] = sf;
+        else if constexpr (!WO) a.blast_partial[3 * (size_t)blockIdx.x + threadIdx.x - 2] = sf;
     }
-    for (int e = threadIdx.x; e < 3 * a.Kl; e += NW * 64) {
-        float s = 0.f;
-        for (int w = 0; w < NW; ++w)
-            s += reinterpret_cast<const float*>(smem + a.lds_wave + w * a.lds_wave_bytes + 2048 + NS * C::MSET * 4)[e];
-        a.wlast_partial[(size_t)blockIdx.x * 3 * a.Kl + e] = s;
+    if constexpr (!WO) {
+        for (int e = threadIdx.x; e < 3 * a.Kl; e += NW * 64) {
+            float s = 0.f;
+            for (int w = 0; w < NW; ++w)
+                s += reinterpret_cast<const float*>(smem + a.lds_wave + w * a.lds_wave_bytes + 2048 + NS * C::MSET * 4)[e];
+            a.wlast_partial[(size_t)blockIdx.x * 3 * a.Kl + e] = s;
+        }
     }
 }
 
@@ -1939,6 +1953,13 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void k_step2dz(Step2Args a) {
 template <int HM, int NW, int MAXR, int NK0F, int NTAF>
 __global__ __launch_bounds__(NW * 64, NW / 4) void k_step2h(Step2Args a) {
     k_step2_body<HM, true, NW, MAXR, NK0F, NTAF, false, true>(a);
+}
+
+// warp-only (a frozen image: marf_warp_step_forward): k_step2's forward, loss, dgrad and dH partials,
+// nothing saved and no last-layer weight gradient (k_step2_body's WO)
+template <int HM, bool SPLIT, int NW, int MAXR, int NK0F = 0, int NTAF = 0>
+__global__ __launch_bounds__(NW * 64, NW / 4) void k_step2w(Step2Args a) {
+    k_step2_body<HM, SPLIT, NW, MAXR, NK0F, NTAF, false, false, true>(a);
 }
 
 // permuted k (hidden operand from an accumulator): k-step ks, lane half hh, element j
@@ -2081,6 +2102,24 @@ static hipError_t launch_step2_t(const Step2Args& a, int grid, hipStream_t s) {
     else
         hipLaunchKernelGGL((k_step2<HM, SPLIT, NW, MAXR, NK0F, NTAF>), dim3(grid), dim3(NW * 64), (size_t)a.lds_total, s, a);
     return hipGetLastError();
+}
+
+template <int NK0F, int NTAF>
+static hipError_t launch_step2w_t(const Step2Args& a, int grid, hipStream_t s) {
+    hipError_t e = ensure_dynamic_lds((const void*)k_step2w<256, true, 4, 4, NK0F, NTAF>, (size_t)a.lds_total);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_step2w<256, true, 4, 4, NK0F, NTAF>), dim3(grid), dim3(256), (size_t)a.lds_total, s, a);
+    return hipGetLastError();
+}
+
+// the warp-only step of the bf16 split recipe (variant 1 of marf_launch_step2, not dz): the same
+// choice of instantiation by (full_nk0, a.nta), or the generic kernel
+hipError_t marf_launch_step2_warp(const Step2Args& a, int grid, hipStream_t s, int full_nk0) {
+    if (full_nk0 == 5 && a.nta == 3) return launch_step2w_t<5, 3>(a, grid, s);
+    if (full_nk0 == 5 && a.nta == 2) return launch_step2w_t<5, 2>(a, grid, s);
+    if (full_nk0 == 4 && a.nta == 2) return launch_step2w_t<4, 2>(a, grid, s);
+    if (full_nk0 == 3 && a.nta == 2) return launch_step2w_t<3, 2>(a, grid, s);
+    return launch_step2w_t<0, 0>(a, grid, s);
 }
 
 // variant: 0 = plain bf16, 256-wide, 8 waves; 1 = split bf16, 256-wide, 4 waves; 2 = plain bf16,

@@ -61,7 +61,10 @@ MARF_DEV void tile_prologue_split(const NetDev& net, const GeoDev& geo, int c2f_
 
 // FWD: the render (marf_render): forward only, any geometry, rgb out, nothing saved; the training
 // forward's instructions on the same pixels, so the same bits.
-template <int TP, bool FWD>
+// WO: warp-only (a frozen image, marf_warp_step_forward): the training step with no tile queued for
+// saving and no last-layer weight / bias gradient partials; the ReLU records stay (the dgrad re-reads
+// them).
+template <int TP, bool FWD, bool WO = false>
 __global__ __launch_bounds__(256, 1) void k_mlp_step_split(StepArgs a) {
     typedef PrecBF16 P;
     constexpr int NW = 4;
@@ -102,7 +105,7 @@ __global__ __launch_bounds__(256, 1) void k_mlp_step_split(StepArgs a) {
 
     // the saved tiles stream out after the GEMM that reads the tile
     auto save = [&](void* dst, int cols) {
-        if constexpr (!FWD) v.template queue_save<NW>(dst, slot0, 0, TP, cols);
+        if constexpr (!FWD && !WO) v.template queue_save<NW>(dst, slot0, 0, TP, cols);
     };
     save(a.feat[0], net.Kp[0]);
 
@@ -130,8 +133,8 @@ __global__ __launch_bounds__(256, 1) void k_mlp_step_split(StepArgs a) {
             step_loss_slots<P, TP, NW>(a, acc, wave, lane, b, p0, gl, gT, lsum);
         }
         __syncthreads();
-        step_tile_partials<TP>(a, wave, lane, gl, lsum);
-        step_wlast_grad<P, TP, NW>(a, Kl, v.feat(), v.lda, wave, lane, gT);  // B = the hi plane
+        step_tile_partials<TP, !WO>(a, wave, lane, gl, lsum);
+        if constexpr (!WO) step_wlast_grad<P, TP, NW>(a, Kl, v.feat(), v.lda, wave, lane, gT);  // B = the hi plane
         __syncthreads();  // feat_{n-1} consumed
         step_fill_d<TP>(v, gl, net.Mt[nl - 1], 0);
         __syncthreads();
@@ -163,16 +166,22 @@ __global__ __launch_bounds__(256, 1) void k_mlp_step_split(StepArgs a) {
 
 using namespace marf;
 
-template <int TP, bool FWD>
+template <int TP, bool FWD, bool WO = false>
 static hipError_t launch_split(const StepArgs& a, size_t lds, int n_tiles, hipStream_t s) {
-    hipError_t e = ensure_dynamic_lds((const void*)k_mlp_step_split<TP, FWD>, lds);
+    hipError_t e = ensure_dynamic_lds((const void*)k_mlp_step_split<TP, FWD, WO>, lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_mlp_step_split<TP, FWD>), dim3(n_tiles), dim3(256), lds, s, a);
+    hipLaunchKernelGGL((k_mlp_step_split<TP, FWD, WO>), dim3(n_tiles), dim3(256), lds, s, a);
     return hipGetLastError();
 }
 
-// TP: 64 (hidden widths above 256) or 128; fwd_only: the render instantiation
-hipError_t marf_launch_mlp_step_split(const StepArgs& a, int TP, bool fwd_only, size_t lds, int n_tiles, hipStream_t s) {
+// TP: 64 (hidden widths above 256) or 128; fwd_only: the render instantiation; warp_only: the WO one
+hipError_t marf_launch_mlp_step_split(const StepArgs& a, int TP, bool fwd_only, size_t lds, int n_tiles, hipStream_t s,
+                                      bool warp_only) {
+    if (warp_only && !fwd_only) {
+        if (TP == 64) return launch_split<64, false, true>(a, lds, n_tiles, s);
+        if (TP == 128) return launch_split<128, false, true>(a, lds, n_tiles, s);
+        return hipErrorInvalidValue;
+    }
     if (TP == 64) return fwd_only ? launch_split<64, true>(a, lds, n_tiles, s) : launch_split<64, false>(a, lds, n_tiles, s);
     if (TP == 128) return fwd_only ? launch_split<128, true>(a, lds, n_tiles, s) : launch_split<128, false>(a, lds, n_tiles, s);
     return hipErrorInvalidValue;

@@ -70,6 +70,11 @@ _SIGS = {
                                     _c_vp]),
     "marf_step_backward_ev": (_c_int, [_c_vp, ctypes.POINTER(Geometry), _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_vp,
                                        _c_vp, ctypes.POINTER(_c_vp), _c_vp]),
+    "marf_warp_step_saved_bytes": (_c_sz, [_c_vp, ctypes.POINTER(Geometry)]),
+    "marf_warp_step_forward": (_c_int, [_c_vp, ctypes.POINTER(Geometry), ctypes.POINTER(C2f), _c_vp, _c_vp, _c_vp, _c_vp,
+                                        _c_vp, _c_vp, _c_vp, _c_vp]),
+    "marf_warp_step_backward": (_c_int, [_c_vp, ctypes.POINTER(Geometry), _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_vp,
+                                         _c_vp]),
     "marf_net_layer_count": (_c_int, [_c_vp]),
     "marf_net_layer_span": (_c_int, [_c_vp, _c_int, ctypes.POINTER(_c_ll), ctypes.POINTER(_c_ll)]),
     "marf_comm_unique_id": (_c_int, [_c_vp, _c_sz]),
@@ -443,6 +448,13 @@ class Net:
     def workspace_bytes(self, geo):
         return lib().marf_workspace_bytes(self._h, ctypes.byref(geo))
 
+    def warp_step_saved_bytes(self, geo):
+        """marf_warp_step_saved_bytes; a net with no warp-only kernel raises with the library's reason."""
+        n = lib().marf_warp_step_saved_bytes(self._h, ctypes.byref(geo))
+        if n == 0:
+            raise RuntimeError("libmarf: " + lib().marf_last_error().decode())
+        return n
+
 
 def grid_geometry(B, H, W, patch_H, patch_W, Hm=None, crop=True):
     """Centre-crop pixel grid (crop) or every canvas pixel (use_cropped_images off, warp.py:54-68)."""
@@ -700,6 +712,87 @@ class _PlanarStepFunction(torch.autograd.Function):
 def render_step(warp_weight, progress, engine, params, gt, mask, denom_override=None, b0=0, b1=None):
     b1 = warp_weight.shape[0] if b1 is None else b1
     return _PlanarStepFunction.apply(warp_weight, progress, engine, b0, b1, gt, mask, denom_override, *params)
+
+
+class _PlanarWarpStepFunction(torch.autograd.Function):
+    """_PlanarStepFunction for a frozen image (marf_warp_step_forward / _backward): the same rgb and
+    loss_rgb, gradients to the warps and to a soft mask only.  The MLP parameters are inputs for
+    packing, never differentiated; the step keeps no activations, so a gradient that reaches rgb
+    directly cannot be served (the general path differentiates the image too) and raises."""
+
+    @staticmethod
+    def forward(ctx, warp_weight, progress, engine, b0, b1, gt, mask, denom_override, *params):
+        ctx.set_materialize_grads(False)
+        w = _f32(warp_weight, "warp_param")
+        Bl = b1 - b0
+        h_local = w[b0:b1].contiguous()
+        Hm = torch.empty(Bl, 3, 3, device=w.device, dtype=torch.float32)
+        st = _stream(w)
+        _check(lib().marf_sl3_to_SL3(_ptr(h_local), _ptr(Hm), Bl, engine.lie_batch(w.shape[0]), st))
+        geo = engine.grid_geo(Bl, Hm)
+        Np = geo_np(engine)
+        gt = _f32(gt, "labels").reshape(Bl, 3, Np)
+        ctx.mask_shape = None if mask is None else mask.shape
+        mask = None if mask is None else _f32(mask, "masks").reshape(Bl, 1, Np)
+        rgb = torch.empty(Bl, Np, 3, device=w.device, dtype=torch.float32)
+        stats = torch.empty(3, device=w.device, dtype=torch.float32)
+        packed = engine.packed_for(params)
+        saved = _BUFS.get("planar_warp_step", engine.net.warp_step_saved_bytes(geo), w.device)
+        cf = make_c2f(progress, engine.c2f)
+        _check(lib().marf_warp_step_forward(engine.net.handle, ctypes.byref(geo), ctypes.byref(cf), _ptr(packed),
+                                            _ptr(gt), _ptr(mask), _ptr(denom_override), _ptr(rgb), _ptr(stats),
+                                            _ptr(saved), st))
+        ctx.save_for_backward(w, rgb, stats)
+        ctx.Hm, ctx.h_local, ctx.saved_buf, ctx.engine = Hm, h_local, saved, engine
+        ctx.gen = _BUFS.generation("planar_warp_step", w.device)
+        ctx.gt, ctx.mask = gt, mask
+        ctx.b0, ctx.b1 = b0, b1
+        ctx.n_params = len(params)
+        engine.last_stats = stats  # [loss, denominator, local 3*sum(mask)]
+        return rgb, stats[0]
+
+    @staticmethod
+    def backward(ctx, d_rgb, d_loss):
+        w, rgb, stats = ctx.saved_tensors
+        engine = ctx.engine
+        n_in = 8 + ctx.n_params
+        if d_rgb is not None:
+            raise RuntimeError("libmarf: render_warp_step keeps no activations, so a gradient reaching rgb directly "
+                               "cannot be propagated (the general path differentiates the image as well); "
+                               "differentiate loss_rgb, or use render_step")
+        if d_loss is None:
+            return (None,) * n_in
+        if ctx.gen != _BUFS.generation("planar_warp_step", w.device):
+            raise RuntimeError("libmarf: the warp-only step's saved buffer was reused by a later forward; "
+                               "call backward() before the next Graph.forward")
+        Bl = ctx.b1 - ctx.b0
+        geo = engine.grid_geo(Bl, ctx.Hm)
+        dh_local = torch.empty(Bl, 8, device=w.device, dtype=torch.float32)
+        gout = _f32(d_loss.reshape(1).to(torch.float32), "grad")
+        _check(lib().marf_warp_step_backward(engine.net.handle, ctypes.byref(geo), _ptr(ctx.saved_buf), _ptr(ctx.h_local),
+                                             engine.lie_batch(w.shape[0]), _ptr(gout), _ptr(stats), _ptr(dh_local),
+                                             _stream(w)))
+        if Bl == w.shape[0]:
+            dw = dh_local
+        else:
+            dw = torch.zeros_like(w)
+            dw[ctx.b0:ctx.b1] = dh_local
+        d_mask = None
+        if ctx.mask is not None and ctx.needs_input_grad[6]:
+            # a learned (soft) mask: d (d_loss * loss) / d m from the step's own prediction and stats
+            d_mask = torch.empty_like(ctx.mask)
+            _check(lib().marf_masked_mse_mask_backward(_ptr(rgb), _ptr(ctx.gt), _ptr(ctx.mask), Bl, ctx.mask.shape[2],
+                                                       _ptr(stats), _ptr(gout), _ptr(d_mask), _stream(w)))
+            d_mask = d_mask.view(ctx.mask_shape)
+        return (dw, None, None, None, None, None, d_mask, None) + (None,) * ctx.n_params
+
+
+def render_warp_step(warp_weight, progress, engine, params, gt, mask, denom_override=None, b0=0, b1=None):
+    """render_step on a frozen image: rgb and loss_rgb with gradients to warp_weight and to a soft mask
+    that requires grad; params are packed, never differentiated."""
+    b1 = warp_weight.shape[0] if b1 is None else b1
+    return _PlanarWarpStepFunction.apply(warp_weight, progress, engine, b0, b1, gt, mask, denom_override,
+                                         *[p.detach() for p in params])
 
 
 def geo_np(engine):

@@ -152,6 +152,10 @@ class Model(torch.nn.Module):
     def build_networks(self):
         log.info("building networks...")
         self.graph = Graph(self.opt).to(self.opt.device)
+        if self.opt.get("load"):
+            # a trained model: with freeze_image its image alone (the patches to register are new ones,
+            # their count may differ), otherwise the whole graph and the iteration
+            self.load_checkpoint(self.opt.load, image_only=bool(self.opt.get("freeze_image")))
         if self.world > 1:
             self.graph.set_shard(self.rank, self.world, self.images)
             if self.opt.device != "cpu":
@@ -162,6 +166,8 @@ class Model(torch.nn.Module):
         opt = self.opt
         groups = [dict(params=self.graph.neural_image.parameters(), lr=opt.optim.lr),
                   dict(params=self.graph.warp_param.parameters(), lr=opt.optim.lr_warp)]
+        if opt.get("freeze_image"):  # the image does not move: the warps (and the mask net, below) only
+            groups = groups[1:]
         if opt.use_implicit_mask:
             # the shared mask network at its own rate (model/planar.py:95-96); embedding_view is in
             # no group, as in the reference: it keeps its random init
@@ -215,7 +221,34 @@ class Model(torch.nn.Module):
             self.tb.close()
         if self.metrics_file:
             self.metrics_file.close()
+        if self.rank == 0 and self.opt.get("save_ckpt"):
+            self.save_checkpoint(os.path.join(self.opt.output_path, "model.ckpt"))
         log.title("TRAINING DONE")
+
+    # ------------------------------------------------------------------ checkpoints
+    def save_checkpoint(self, path):
+        """The graph's state dict (neural_image.*, warp_param.weight, the mask modules) and `it`."""
+        sd = {k: v.detach().cpu() for k, v in self.graph.state_dict().items()}
+        torch.save(dict(graph=sd, it=int(self.it)), path)
+
+    def load_checkpoint(self, path, image_only=False):
+        """The reverse of save_checkpoint.  image_only: restore neural_image.* alone (a frozen image for
+        new patches: the warps, their count and the iteration are this run's own)."""
+        ck = torch.load(path, map_location="cpu")
+        sd = ck["graph"]
+        if image_only:
+            sub = {k[len("neural_image."):]: v for k, v in sd.items() if k.startswith("neural_image.")}
+            if not sub:
+                raise RuntimeError(f"{path}: no neural_image.* entries")
+            with torch.no_grad():
+                self.graph.neural_image.load_state_dict(sub, strict=True)
+        else:
+            with torch.no_grad():
+                self.graph.load_state_dict(sd, strict=True)
+            self.it = int(ck.get("it", 0))
+            self.graph.it = self.it
+        marf_hip.PARAM_GENERATION[0] += 1  # (the engines re-pack the weights)
+        return ck
 
     def summarize_loss(self, loss):
         """all = sum_k 10^w_k loss_k with NaN / Inf checks (model/planar.py:172-185)."""
@@ -242,7 +275,7 @@ class Model(torch.nn.Module):
         process, the fused step, no edge term (its alpha = it / max_iter is a host value), no
         learning-rate scheduler, the library's Adam (its per-step scalars come from a device table)."""
         return (self.world == 1 and not self.opt.use_edges and not self.opt.use_implicit_mask
-                and self.opt.get("fused_step", True)
+                and self.opt.get("fused_step", True) and not self.opt.get("freeze_image")
                 and str(self.opt.device).startswith("cuda") and not self.sched
                 and isinstance(self.optim, marf_hip.Adam))
 
@@ -353,7 +386,7 @@ class Model(torch.nn.Module):
         (one all-reduce of the whole vector) covers the unfused step and MARF_GRAD_BUCKETS=0.
         MARF_GRAD_COMM=marf exchanges through the C ABI's own RCCL communicator (marf_comm_*) instead
         of torch.distributed's."""
-        if self.world <= 1:
+        if self.world <= 1 or self.opt.get("freeze_image"):  # (a frozen image has no gradient to exchange)
             return
         grads = [p.grad for p in self.graph.neural_image.mlp.parameters()]
         flat = marf_hip.flat_view(grads)
@@ -555,6 +588,27 @@ class Graph(torch.nn.Module):
         self.loss_denominator = None
         self.edge_denominator = None
         self.need_edges = True
+        self.freeze_image = bool(opt.get("freeze_image"))
+        if self.freeze_image:
+            # register patches on a trained image: the warps (and a learned mask) move, the image does
+            # not.  The training forward is the warp-only fused step (marf_hip.render_warp_step).
+            if _dist() and torch.distributed.get_world_size() > 1:
+                raise NotImplementedError("freeze_image with more than one rank: the warp-only step is single-process "
+                                          "(there is no MLP gradient to exchange, and the shard's loss denominator "
+                                          "path is not wired for it)")
+            if opt.get("cuda_graph"):
+                raise NotImplementedError("freeze_image with cuda_graph: the captured iteration records the full "
+                                          "step; turn cuda_graph off")
+            if _precision(opt) == marf_hip.MARF_FP16X2:
+                raise NotImplementedError("freeze_image with precision fp16x2: k_step2h has no warp-only "
+                                          "instantiation; use bf16x3")
+            if os.environ.get("MARF_STEP2_DZ", "")[:1] == "1":
+                raise NotImplementedError("freeze_image with MARF_STEP2_DZ=1: k_step2dz has no warp-only "
+                                          "instantiation; unset MARF_STEP2_DZ")
+            if not opt.get("fused_step", True):
+                raise NotImplementedError("freeze_image needs the fused step (fused_step: true): the separate "
+                                          "forward / backward kernels differentiate the image")
+            self.neural_image.requires_grad_(False)
 
     def warp_h(self):
         """The warps as the reference's sl(3) parameters [B, 8] (se2: the embedded generators)."""
@@ -634,7 +688,8 @@ class Graph(torch.nn.Module):
             else:
                 masks = imgs.masks[b0:b1] if imgs.get("masks") is not None else None
             denom = self.loss_denominator if self.shard is not None else None
-            rgb, loss_rgb = self.neural_image.render_step(self.warp_h(), imgs.rgb[b0:b1], masks, denom, b0, b1)
+            step = self.neural_image.render_warp_step if self.freeze_image else self.neural_image.render_step
+            rgb, loss_rgb = step(self.warp_h(), imgs.rgb[b0:b1], masks, denom, b0, b1)
             var.fused_loss = (loss_rgb, imgs.rgb, var.mask_prediction if implicit else imgs.get("masks"))
         else:
             rgb = self.neural_image.render(self.warp_h(), b0, b1)  # [Bl, h*w, 3]
@@ -831,6 +886,13 @@ class NeuralImageFunction(torch.nn.Module):
         ps = self._params()
         return marf_hip.render_step(warp_weight, self.progress.detach(), self.engine(warp_weight.device), ps, gt, masks,
                                     denom, b0, b1)
+
+    def render_warp_step(self, warp_weight, gt, masks, denom=None, b0=0, b1=None):
+        """render_step of a frozen image (freeze_image): the same (rgb, loss_rgb), gradients to the warps
+        and a learned mask only, nothing kept for weight gradients."""
+        ps = self._params()
+        return marf_hip.render_warp_step(warp_weight, self.progress.detach(), self.engine(warp_weight.device), ps, gt,
+                                         masks, denom, b0, b1)
 
     def forward(self, coord_2d):
         """rgb = MLP(cat[coord, posenc(coord)]) for explicit coordinates [..., 2] (:429-449)."""

@@ -1,6 +1,7 @@
 """Static instruction census of the step kernel's hot regions in a hipcc -S listing.
 
     python tools/isa_census.py <file.s> [mangled kernel name]
+    python tools/isa_census.py --stores <file.s> [mangled kernel name]   (the kernel's vector global stores by opcode)
 
 (default kernel: k_step2<256, true, 4, 4, 5, 3>, the instantiation bench.py runs).  Three regions,
 found from the control flow and the MFMA shapes alone:
@@ -78,10 +79,23 @@ def report(title, ins):
     print(f"   non-MFMA per MFMA {tot / m:.2f}")
 
 
+def stores(ins):
+    """Vector global stores of a whole kernel, by opcode (static count: an instruction in a loop is one)."""
+    c = Counter(t.split()[0] for t in ins if t.startswith(("global_store", "global_atomic", "buffer_store", "flat_store",
+                                                           "scratch_store")))
+    return c
+
+
 def main():
-    path = sys.argv[1]
-    name = sys.argv[2] if len(sys.argv) > 2 else FLAGSHIP
+    args = [a for a in sys.argv[1:] if a != "--stores"]
+    path = args[0]
+    name = args[1] if len(args) > 1 else FLAGSHIP
     ins = kernel_lines(path, name)
+    if "--stores" in sys.argv:  # python tools/isa_census.py --stores <file.s> [kernel]: the store census alone
+        c = stores(ins)
+        print(f"== {name}: {sum(c.values())} vector global store instructions: " +
+              (", ".join(f"{k} {v}" for k, v in sorted(c.items())) or "none"))
+        return
     label = {t[:-1]: i for i, t in enumerate(ins) if t.endswith(":")}
     big = [i for i, t in enumerate(ins) if t.startswith("v_mfma_f32_32x32x16")]
     loops = []
