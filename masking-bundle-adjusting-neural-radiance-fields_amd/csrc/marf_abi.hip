@@ -43,6 +43,29 @@ static int check_hip(hipError_t e, const char* what) {
 
 static inline long long rup(long long x, long long m) { return (x + m - 1) / m * m; }
 
+// A buffer plan is a run of take() calls: each returns its region's byte offset and advances by the
+// size rounded up to 256 B (take(0): the offset, nothing advanced), so the order of the calls is the
+// order in memory.  On the stack: the plans run at every forward and backward call.
+struct Layout {
+    size_t off = 0;
+    size_t take(long long bytes) {
+        const size_t at = off;
+        off += (size_t)rup(bytes, 256);
+        return at;
+    }
+};
+
+// The split-K rule of the weight gradients over S pixel slots: about `div` chunks of a multiple of
+// 64 slots (div = 256; 1024 for the bandwidth-bound last layer of the unfused path).  The one copy:
+// the plans size the partials by it and the launches write them by it.
+struct SplitK {
+    int chunk, n;
+};
+static SplitK split_k(long long S, int div) {
+    const long long chunk = std::max(64LL, rup((S + div - 1) / div, 64));
+    return {(int)chunk, (int)((S + chunk - 1) / chunk)};
+}
+
 // step2 plan (the pixel-per-wave fused step, marf_step2.hip), filled by plan_step2_net
 struct Step2NetPlan {
     int variant;           // -1: not available for this net; 0: bf16 (8 waves); 1: split bf16 (4 waves);
@@ -60,22 +83,85 @@ struct Step2NetPlan {
     size_t prog_off, bias_off, kmap_off, end_off;
 };
 
-struct marf_net {
-    int n_layers, L, D, dtype;
-    unsigned skip;  // bit l: layer l's input is [feature ; posenc] (model/planar.py:419-420, 440-441)
-    int kin[MARF_MAX_LAYERS];  // true input width of layer l (dims[l], + D for a skip layer)
-    int kdt;  // kernel arithmetic of the generic kernels: 0 fp32, 1 bf16 (MARF_BF16 and MARF_BF16X3), 2 fp16
-    Step2NetPlan s2;
+// The shape and padding of an MLP in the tile kernels' layouts (marf_common.h): what the image
+// network and the mask network share, and what the unfused path's plans and packing are written over.
+struct NetShape {
+    int n_layers;
+    int kdt;   // kernel arithmetic of the generic kernels: 0 fp32, 1 bf16 (MARF_BF16 and MARF_BF16X3), 2 fp16
+    int elem;  // bytes per stored element
     int dims[MARF_MAX_LAYERS + 1];
+    int kin[MARF_MAX_LAYERS];  // true input width of layer l (dims[l], + D for a skip layer)
     int Kp[MARF_MAX_LAYERS], Mp[MARF_MAX_LAYERS], Mt[MARF_MAX_LAYERS];
     long long w_off[MARF_MAX_LAYERS], b_off[MARF_MAX_LAYERS], param_count;
     long long wf_off[MARF_MAX_LAYERS], wt_off[MARF_MAX_LAYERS], bias_off[MARF_MAX_LAYERS];
     size_t packed_bytes;
-    int TP, lda, Kmax;
+    int TP, lda;
+};
+
+// W_l then b_l in the flat parameter vector; Wf_l, Wt_l, bias_l in the packed buffer (pelem: bytes
+// per packed weight).  dims, kin, Kp, Mp, Mt are set.
+static void plan_params(NetShape& n, int pelem) {
+    long long off = 0;
+    Layout at;
+    for (int l = 0; l < n.n_layers; ++l) {
+        n.w_off[l] = off;
+        off += (long long)n.dims[l + 1] * n.kin[l];
+        n.b_off[l] = off;
+        off += n.dims[l + 1];
+        n.wf_off[l] = (long long)at.take((long long)n.Mp[l] * n.Kp[l] * pelem);
+        n.wt_off[l] = (long long)at.take((long long)n.Kp[l] * n.Mt[l] * pelem);
+        n.bias_off[l] = (long long)at.take((long long)n.Mp[l] * 4);
+    }
+    n.param_count = off;
+    n.packed_bytes = at.off;
+}
+
+// the pack kernel's arguments; returns the largest layer's element count (its grid)
+static long long fill_pack_args(const NetShape& n, PackArgs& a) {
+    memset(&a, 0, sizeof(a));
+    a.n_layers = n.n_layers;
+    long long mx = 0;
+    for (int l = 0; l < n.n_layers; ++l) {
+        PackLayer& p = a.ly[l];
+        p.M = n.dims[l + 1];
+        p.K = n.kin[l];
+        p.Mp = n.Mp[l];
+        p.Kp = n.Kp[l];
+        p.Mt = n.Mt[l];
+        p.w_off = n.w_off[l];
+        p.b_off = n.b_off[l];
+        p.wf_off = n.wf_off[l];
+        p.wt_off = n.wt_off[l];
+        p.bias_off = n.bias_off[l];
+        mx = std::max(mx, (long long)p.Mp * p.Kp + (long long)p.Kp * p.Mt + p.Mp);
+    }
+    return mx;
+}
+
+// L: the posenc frequencies of the net's input (the image net's L, the mask net's n_freqs)
+static void fill_netdev(const NetShape& n, int L, const void* packed, NetDev& d) {
+    memset(&d, 0, sizeof(d));
+    d.n_layers = n.n_layers;
+    d.L = L;
+    d.D = n.dims[0];
+    for (int l = 0; l < n.n_layers; ++l) {
+        d.Kp[l] = n.Kp[l];
+        d.Mp[l] = n.Mp[l];
+        d.Mt[l] = n.Mt[l];
+        d.Wf[l] = (const char*)packed + n.wf_off[l];
+        d.Wt[l] = (const char*)packed + n.wt_off[l];
+        d.bias[l] = (const float*)((const char*)packed + n.bias_off[l]);
+    }
+}
+
+struct marf_net : NetShape {
+    int L, D, dtype;
+    unsigned skip;  // bit l: layer l's input is [feature ; posenc] (model/planar.py:419-420, 440-441)
+    Step2NetPlan s2;
+    int Kmax;
     int sTP, sNW;  // the fused step's tile (pixel slots) and waves per block (k_mlp_step)
     bool tsplit;   // MARF_BF16X3 on the split tile kernel (k_mlp_step_split): a net k_step2 cannot hold
     size_t lds_fwd, lds_bwd, lds_step;
-    int elem;  // bytes per stored element
     unsigned diag[MARF_MAX_LAYERS];  // numerics-experiment rounding codes (MARF_DIAG_PREC; MARF_DIAG_RT builds)
     int pipe_mode, pipe_wg, pipe_piece;  // pipelined weight gradients (marf_net_set_pipeline)
 };
@@ -504,23 +590,7 @@ int marf_net_create_skip(int n_layers, const int* dims, int L, int dtype, long l
         return fail(MARF_ERR_UNSUPPORTED, "net_create: tile does not fit LDS (%zu B dynamic + %zu B static)", n->lds_bwd,
                     static4);
     }
-    long long off = 0;
-    size_t boff = 0;
-    const int pelem = n->tsplit ? 2 * n->elem : n->elem;  // bytes per packed weight (split: hi + lo image)
-    for (int l = 0; l < n_layers; ++l) {
-        n->w_off[l] = off;
-        off += (long long)dims[l + 1] * n->kin[l];
-        n->b_off[l] = off;
-        off += dims[l + 1];
-        n->wf_off[l] = (long long)boff;
-        boff += rup((long long)n->Mp[l] * n->Kp[l] * pelem, 256);
-        n->wt_off[l] = (long long)boff;
-        boff += rup((long long)n->Kp[l] * n->Mt[l] * pelem, 256);
-        n->bias_off[l] = (long long)boff;
-        boff += rup((long long)n->Mp[l] * 4, 256);
-    }
-    n->param_count = off;
-    n->packed_bytes = boff;
+    plan_params(*n, n->tsplit ? 2 * n->elem : n->elem);  // (split: a hi and a lo image per packed weight)
     parse_diag(n);
     plan_step2_net(n, pixels_hint);
     {  // defaults of the pipelined weight gradients (marf_net_set_pipeline changes them)
@@ -579,24 +649,8 @@ const char* marf_net_step_kernel(const marf_net* net) {
 int marf_net_pack(const marf_net* net, const float* d_params, void* d_packed, void* stream) {
     if (!net || !d_params || !d_packed) return fail(MARF_ERR_INVALID, "net_pack: NULL argument");
     PackArgs a;
-    memset(&a, 0, sizeof(a));
-    a.n_layers = net->n_layers;
-    long long mx = 0;
-    for (int l = 0; l < net->n_layers; ++l) {
-        PackLayer& p = a.ly[l];
-        p.M = net->dims[l + 1];
-        p.K = net->kin[l];
-        p.Mp = net->Mp[l];
-        p.Kp = net->Kp[l];
-        p.Mt = net->Mt[l];
-        p.w_off = net->w_off[l];
-        p.b_off = net->b_off[l];
-        p.wf_off = net->wf_off[l];
-        p.wt_off = net->wt_off[l];
-        p.bias_off = net->bias_off[l];
-        p.diag = net->diag[l];
-        mx = std::max(mx, (long long)p.Mp * p.Kp + (long long)p.Kp * p.Mt + p.Mp);
-    }
+    const long long mx = fill_pack_args(*net, a);
+    for (int l = 0; l < net->n_layers; ++l) a.ly[l].diag = net->diag[l];
     MarfProfScope ps("pack_weights", (hipStream_t)stream);
     // the tile kernels' layouts (Wf / Wt / bias): every path of a k_step2 net runs its program
     // instead (marf_forward / marf_backward refuse the split recipes), so it packs that one only; the
@@ -639,87 +693,62 @@ int marf_net_pack(const marf_net* net, const float* d_params, void* d_packed, vo
 }
 
 static void fill_netdev(const marf_net* n, const void* packed, NetDev& d) {
-    memset(&d, 0, sizeof(d));
-    d.n_layers = n->n_layers;
-    d.L = n->L;
-    d.D = n->D;
-    for (int l = 0; l < n->n_layers; ++l) {
-        d.Kp[l] = n->Kp[l];
-        d.Mp[l] = n->Mp[l];
-        d.Mt[l] = n->Mt[l];
-        d.Wf[l] = (const char*)packed + n->wf_off[l];
-        d.Wt[l] = (const char*)packed + n->wt_off[l];
-        d.bias[l] = (const float*)((const char*)packed + n->bias_off[l]);
-        d.diag[l] = n->diag[l];
-    }
+    fill_netdev(*n, n->L, packed, d);
+    for (int l = 0; l < n->n_layers; ++l) d.diag[l] = n->diag[l];
     d.skip = n->skip;
 }
 
 // ------------------------------------------------------------------ buffer plans
 
+// the unfused path (marf_forward / marf_backward, marf_mask_forward / marf_mask_backward)
 struct SavedPlan {
     size_t feat[MARF_MAX_LAYERS], mask[MARF_MAX_LAYERS], total;
 };
 
-static void plan_saved(const marf_net* n, long long S, SavedPlan& p) {
-    size_t off = 0;
-    for (int l = 0; l < n->n_layers; ++l) {
-        p.feat[l] = off;
-        off += rup((long long)S * n->Kp[l] * n->elem, 256);
-    }
+static void plan_saved(const NetShape& n, long long S, SavedPlan& p) {
+    Layout at;
+    for (int l = 0; l < n.n_layers; ++l) p.feat[l] = at.take(S * n.Kp[l] * n.elem);
     p.mask[0] = 0;
-    for (int l = 1; l < n->n_layers; ++l) {
-        p.mask[l] = off;
-        off += rup(S / n->TP * 4096, 256);  // mask records: one uint4 per lane per wave per tile
+    for (int l = 1; l < n.n_layers; ++l) p.mask[l] = at.take(S / n.TP * 4096);  // one uint4 per lane per wave per tile
+    p.total = at.off;
+}
+
+// the largest hidden / layer-0 weight gradient (Mp x K) and bias gradient (Mp) of a net, in
+// elements: what one split-K chunk's partial holds (K0: the width of feat_0's rows)
+static void max_partial(const NetShape& n, int K0, long long& mxo, long long& mxm) {
+    mxo = mxm = 0;
+    for (int l = 0; l < n.n_layers - 1; ++l) {
+        mxo = std::max(mxo, (long long)n.Mp[l] * (l == 0 ? K0 : n.Kp[l]));
+        mxm = std::max(mxm, (long long)n.Mp[l]);
     }
-    p.total = off;
 }
 
 struct WsPlan {
     size_t dz[MARF_MAX_LAYERS], glast, dH, part, bpart, total;
-    int chunk, n_chunks, n_tiles;
-    int chunk_last, n_chunks_last;  // finer split for the bandwidth-bound last-layer wgrad
+    SplitK k, k_last;  // (a finer split for the bandwidth-bound last-layer wgrad)
 };
 
-static void plan_ws(const marf_net* n, long long S, int n_tiles, WsPlan& p) {
-    size_t off = 0;
+// dH_tiles: the tiles whose dH partials the workspace holds (the image net; 0: the mask net has none)
+static void plan_ws(const NetShape& n, long long S, long long dH_tiles, WsPlan& p) {
+    Layout at;
     p.dz[0] = 0;
-    for (int l = 1; l < n->n_layers; ++l) {
-        p.dz[l] = off;
-        off += rup((long long)S * n->Kp[l] * n->elem, 256);
-    }
-    p.glast = off;
-    off += rup(S * 16, 256);
-    p.dH = off;
-    off += rup((long long)n_tiles * 9 * 4, 256);
-    long long chunk = rup((S + 255) / 256, 64);
-    if (chunk < 64) chunk = 64;
-    p.chunk = (int)chunk;
-    p.n_chunks = (int)((S + chunk - 1) / chunk);
-    p.n_tiles = n_tiles;
-    long long mxo = 0, mxm = 0;
-    for (int l = 0; l < n->n_layers - 1; ++l) {
-        mxo = std::max(mxo, (long long)n->Mp[l] * n->Kp[l]);
-        mxm = std::max(mxm, (long long)n->Mp[l]);
-    }
-    long long cl = rup((S + 1023) / 1024, 64);
-    if (cl < 64) cl = 64;
-    p.chunk_last = (int)cl;
-    p.n_chunks_last = (int)((S + cl - 1) / cl);
-    long long part_elems = std::max((long long)p.n_chunks * mxo, (long long)p.n_chunks_last * 3 * n->Kp[n->n_layers - 1]);
-    long long bpart_elems = std::max((long long)p.n_chunks * mxm, (long long)p.n_chunks_last * 3);
-    p.part = off;
-    off += rup(part_elems * 4, 256);
-    p.bpart = off;
-    off += rup(bpart_elems * 4, 256);
-    p.total = off;
+    for (int l = 1; l < n.n_layers; ++l) p.dz[l] = at.take(S * n.Kp[l] * n.elem);
+    p.glast = at.take(S * 16);
+    p.dH = at.take(dH_tiles * 9 * 4);
+    p.k = split_k(S, 256);
+    p.k_last = split_k(S, 1024);
+    long long mxo, mxm;
+    max_partial(n, n.Kp[0], mxo, mxm);
+    p.part = at.take(std::max(p.k.n * mxo, (long long)p.k_last.n * 3 * n.Kp[n.n_layers - 1]) * 4);
+    p.bpart = at.take(std::max(p.k.n * mxm, (long long)p.k_last.n * 3) * 4);
+    p.total = at.off;
 }
 
 size_t marf_saved_bytes(const marf_net* net, const marf_geometry* geo) {
     GeoDev g;
     if (!net || make_geo(geo, g, MARF_TILE_PAD) != MARF_OK) return 0;
     SavedPlan p;
-    plan_saved(net, (long long)g.B * g.Np_pad, p);
+    plan_saved(*net, (long long)g.B * g.Np_pad, p);
     return p.total;
 }
 
@@ -728,11 +757,24 @@ size_t marf_workspace_bytes(const marf_net* net, const marf_geometry* geo) {
     if (!net || make_geo(geo, g, MARF_TILE_PAD) != MARF_OK) return 0;
     long long S = (long long)g.B * g.Np_pad;
     WsPlan p;
-    plan_ws(net, S, (int)(S / net->TP), p);
+    plan_ws(*net, S, S / net->TP, p);
     return p.total;
 }
 
 // ------------------------------------------------------------------ forward / backward
+
+// The warp gradient in one launch: the fixed-order sum of the dH partials (per_patch of them per
+// patch) and the Lie backward.  d_gout / denom: the upstream gradient and the loss denominator of a
+// fused step (null: the partials are final).  prof / what: the profile scope and the error text.
+static int launch_warp_bwd(const float* dH_partial, int per_patch, const GeoDev& g, const float* d_h_params,
+                           float* d_dh, int lie_batch, hipStream_t s, const float* d_gout, const float* denom,
+                           const char* prof, const char* what) {
+    MarfProfScope ps(prof, s);
+    HIPCHK(marf_launch_reduce_dH(dH_partial, per_patch, g.B, d_h_params, nullptr, d_dh, lie_batch > 0 ? lie_batch : g.B,
+                                 s, d_gout, denom),
+           what);
+    return MARF_OK;
+}
 
 int marf_forward(const marf_net* net, const marf_geometry* geo, const marf_c2f* c2f, const void* d_packed,
                  float* d_rgb, void* d_saved, void* stream) {
@@ -750,7 +792,7 @@ int marf_forward(const marf_net* net, const marf_geometry* geo, const marf_c2f* 
     a.lda = net->lda;
     if (d_saved) {
         SavedPlan p;
-        plan_saved(net, a.S, p);
+        plan_saved(*net, a.S, p);
         for (int l = 0; l < net->n_layers; ++l) a.feat[l] = (char*)d_saved + p.feat[l];
         for (int l = 1; l < net->n_layers; ++l) a.mask[l] = (uint64_t*)((char*)d_saved + p.mask[l]);
     }
@@ -785,9 +827,9 @@ int marf_backward(const marf_net* net, const marf_geometry* geo, const marf_c2f*
     a.lda = net->lda;
     const int n_tiles = (int)(a.S / net->TP);
     SavedPlan sp;
-    plan_saved(net, a.S, sp);
+    plan_saved(*net, a.S, sp);
     WsPlan wp;
-    plan_ws(net, a.S, n_tiles, wp);
+    plan_ws(*net, a.S, n_tiles, wp);
     char* ws = (char*)d_workspace;
     const char* sv = (const char*)d_saved;
     for (int l = 1; l < net->n_layers; ++l) {
@@ -814,12 +856,12 @@ int marf_backward(const marf_net* net, const marf_geometry* geo, const marf_c2f*
             {
                 MarfProfScope ps(l == 0 ? "wgrad_l0" : "wgrad_hidden", s);
                 HIPCHK(marf_launch_wgrad(net->kdt, ws + wp.dz[l + 1], net->Kp[l + 1], sv + sp.feat[l], net->Kp[l],
-                                         a.S, net->Mp[l], net->Kp[l], wp.chunk, wp.n_chunks, part, bpart, s),
+                                         a.S, net->Mp[l], net->Kp[l], wp.k.chunk, wp.k.n, part, bpart, s),
                        "backward wgrad");
             }
             {
                 MarfProfScope ps("wgrad_reduce", s);
-                HIPCHK(marf_launch_wgrad_reduce(part, bpart, wp.n_chunks, net->Mp[l], net->Kp[l], net->dims[l + 1],
+                HIPCHK(marf_launch_wgrad_reduce(part, bpart, wp.k.n, net->Mp[l], net->Kp[l], net->dims[l + 1],
                                                 net->kin[l], d_dparams + net->w_off[l], d_dparams + net->b_off[l], s),
                        "backward wgrad reduce");
             }
@@ -828,69 +870,64 @@ int marf_backward(const marf_net* net, const marf_geometry* geo, const marf_c2f*
         {
             MarfProfScope ps("wgrad_last", s);
             HIPCHK(marf_launch_wgrad_last(net->kdt, a.glast, sv + sp.feat[l], a.S, net->Kp[l], net->Kp[l],
-                                          wp.chunk_last, wp.n_chunks_last, part, bpart, s),
+                                          wp.k_last.chunk, wp.k_last.n, part, bpart, s),
                    "backward wgrad last");
         }
-        HIPCHK(marf_launch_wgrad_reduce(part, bpart, wp.n_chunks_last, 3, net->Kp[l], 3, net->dims[l],
+        HIPCHK(marf_launch_wgrad_reduce(part, bpart, wp.k_last.n, 3, net->Kp[l], 3, net->dims[l],
                                         d_dparams + net->w_off[l], d_dparams + net->b_off[l], s),
                "backward wgrad last reduce");
     }
-    if (a.geo.mode == MARF_GEO_GRID && d_dh) {
-        MarfProfScope ps("warp_bwd", s);
-        HIPCHK(marf_launch_reduce_dH(a.dH_partial, a.geo.Np_pad / net->TP, a.geo.B, d_h_params, nullptr, d_dh,
-                                     lie_batch > 0 ? lie_batch : a.geo.B, s),
-               "backward warp");
-    }
+    if (a.geo.mode == MARF_GEO_GRID && d_dh)
+        return launch_warp_bwd(a.dH_partial, a.geo.Np_pad / net->TP, a.geo, d_h_params, d_dh, lie_batch, s, nullptr,
+                               nullptr, "warp_bwd", "backward warp");
     return MARF_OK;
 }
 
 // ------------------------------------------------------------------ fused training step
 
+// What a launch of a step kernel is for: the training step (forward, dgrad and what the weight
+// gradients read), a forward-only render, or the warp-only step of a frozen image (forward and
+// dgrad; nothing for a weight gradient).  The plans below state per region which kinds have it.
+enum StepKind { STEP_FULL, STEP_RENDER, STEP_WARP };
+
+// the tile kernels' step buffer (k_mlp_step / k_mlp_step_split): STEP_FULL or STEP_WARP, which keeps
+// the ReLU records (the kernel's own dgrad re-reads them), the per-tile dH and loss partials and
+// the band weights (their renders take no buffer)
 struct StepPlan {
     size_t feat[MARF_MAX_LAYERS], dz[MARF_MAX_LAYERS], mask[MARF_MAX_LAYERS];
     size_t wlast, blast, dH, loss, c2f, part, bpart, total;
-    int n_tiles, chunk, n_chunks;
+    int n_tiles;
+    SplitK k;
 };
 
-static void plan_step(const marf_net* n, long long S, StepPlan& p) {
-    size_t off = 0;
+static void plan_step(const marf_net* n, long long S, StepKind kind, StepPlan& p) {
+    memset(&p, 0, sizeof(p));
+    Layout at;
+    const bool full = kind == STEP_FULL;
     const int nl = n->n_layers;
     p.n_tiles = (int)(S / n->sTP);
-    for (int l = 0; l < nl - 1; ++l) {
-        p.feat[l] = off;
-        off += rup((long long)S * n->Kp[l] * n->elem, 256);
-    }
-    p.dz[0] = p.mask[0] = 0;
+    if (full)
+        for (int l = 0; l < nl - 1; ++l) p.feat[l] = at.take(S * n->Kp[l] * n->elem);
     for (int l = 1; l < nl; ++l) {
-        p.dz[l] = off;
-        off += rup((long long)S * n->Kp[l] * n->elem, 256);
-        p.mask[l] = off;
-        off += rup(S / n->sTP * n->sNW * 1024, 256);  // one uint4 per lane per wave per tile
+        if (full) p.dz[l] = at.take(S * n->Kp[l] * n->elem);
+        p.mask[l] = at.take(S / n->sTP * n->sNW * 1024);  // one uint4 per lane per wave per tile
     }
-    p.wlast = off;
-    off += rup((long long)p.n_tiles * 3 * n->Kp[nl - 1] * 4, 256);
-    p.blast = off;
-    off += rup((long long)p.n_tiles * 3 * 4, 256);
-    p.dH = off;
-    off += rup((long long)p.n_tiles * 9 * 4, 256);
-    p.loss = off;
-    off += rup((long long)p.n_tiles * 2 * 8, 256);
-    p.c2f = off;
-    off += 256;
-    long long chunk = rup((S + 255) / 256, 64);
-    if (chunk < 64) chunk = 64;
-    p.chunk = (int)chunk;
-    p.n_chunks = (int)((S + chunk - 1) / chunk);
-    long long mxo = 0, mxm = 0;
-    for (int l = 0; l < nl - 1; ++l) {
-        mxo = std::max(mxo, (long long)n->Mp[l] * n->Kp[l]);
-        mxm = std::max(mxm, (long long)n->Mp[l]);
+    if (full) {
+        p.wlast = at.take((long long)p.n_tiles * 3 * n->Kp[nl - 1] * 4);
+        p.blast = at.take((long long)p.n_tiles * 3 * 4);
     }
-    p.part = off;  // also the fold scratch of the last-layer reduction: 256 groups x (3 Kp + 3)
-    off += rup(std::max((long long)p.n_chunks * mxo, 256LL * (3 * n->Kp[nl - 1] + 3)) * 4, 256);
-    p.bpart = off;
-    off += rup((long long)p.n_chunks * mxm * 4, 256);
-    p.total = off;
+    p.dH = at.take((long long)p.n_tiles * 9 * 4);
+    p.loss = at.take((long long)p.n_tiles * 2 * 8);
+    p.c2f = at.take(256);
+    if (full) {
+        p.k = split_k(S, 256);
+        long long mxo, mxm;
+        max_partial(*n, n->Kp[0], mxo, mxm);
+        // (part: also the fold scratch of the last-layer reduction: 256 groups x (3 Kp + 3))
+        p.part = at.take(std::max(p.k.n * mxo, 256LL * (3 * n->Kp[nl - 1] + 3)) * 4);
+        p.bpart = at.take(p.k.n * mxm * 4);
+    }
+    p.total = at.off;
 }
 
 // ---- the pixel-per-wave fused step (marf_step2.hip)
@@ -914,6 +951,7 @@ struct Step2BufPlan {
     int grid, n_tiles;
     int nblk;  // per-block partial sets of the step kernel (all pieces' blocks)
     long long S;
+    SplitK k;  // the hidden / layer-0 weight gradients' split over S (pipeline off)
     PipePlan pipe;
     bool fused_res;  // partl / bpartl reserved for the fused weight gradients (step2_backward takes
                      // that path only then)
@@ -948,21 +986,14 @@ static int device_cus() {
 
 static bool use_step2(const marf_net* n) { return n->s2.variant >= 0; }
 
-// split-K chunk of the weight gradients over S pixel slots (k_wgrad / k_wgrad_dma)
-static long long wgrad_chunk(long long S) {
-    long long chunk = rup((S + 255) / 256, 64);
-    return chunk < 64 ? 64 : chunk;
-}
-
 // The layer-0 weight gradient recomputes feat_0 (grid -> warp -> posenc + c2f, bf16 hi) instead of
 // reading it, so the step kernel does not store it (MARF_F0_RECOMPUTE=0: store and read, for A/B).
 static bool l0_recompute(const marf_net* n, const GeoDev& g, long long S) {
     const char* e = getenv("MARF_F0_RECOMPUTE");
     if (e && e[0] == '0') return false;
     if ((n->s2.variant != 1 && n->s2.variant != 3) || g.mode != MARF_GEO_GRID) return false;
-    const long long chunk = wgrad_chunk(S);
-    return marf_wgrad_l0_recompute_ok(n->Mp[0], n->Kp[1], n->s2.ldf0, n->L, S, (int)chunk,
-                                      (int)((S + chunk - 1) / chunk), g.Np_pad);
+    const SplitK k = split_k(S, 256);
+    return marf_wgrad_l0_recompute_ok(n->Mp[0], n->Kp[1], n->s2.ldf0, n->L, S, k.chunk, k.n, g.Np_pad);
 }
 
 // The weight gradient of the last hidden layer (n-2) recomputes dz_{n-1} = relu'(z) (W_{n-1}^T g), a
@@ -979,9 +1010,8 @@ static bool dzl_recompute(const marf_net* n, const GeoDev& g, long long S, bool 
     if (n->s2.variant != 1 || n->s2.dz || pipe_on || g.mode != MARF_GEO_GRID || nl < 3 || n->s2.NMW != 4) return false;
     for (int l = 0; l < nl - 1; ++l)
         if (n->Mp[l] != 256 || (l > 0 && n->Kp[l] != 256)) return false;
-    const long long chunk = wgrad_chunk(S);
-    return marf_wgrad_dzl_ok(n->Mp[nl - 2], n->Kp[nl - 1], n->Kp[nl - 2], n->Kp[nl - 2], S, (int)chunk,
-                             (int)((S + chunk - 1) / chunk));
+    const SplitK k = split_k(S, 256);
+    return marf_wgrad_dzl_ok(n->Mp[nl - 2], n->Kp[nl - 1], n->Kp[nl - 2], n->Kp[nl - 2], S, k.chunk, k.n);
 }
 
 // ---- pipelined weight gradients (large steps of the pixel-per-wave kernel)
@@ -1062,103 +1092,75 @@ static int pipe_streams(PipeStreams** out) {
     return MARF_OK;
 }
 
-// render = a forward-only launch: no saved tensors, no dH / weight-gradient partials
-static void plan_step2_bufs(const marf_net* n, const GeoDev& g, Step2BufPlan& p, bool render = false) {
+// The pixel-per-wave kernels' buffer (k_step2 and its siblings), by kind:
+//   STEP_FULL    every region;
+//   STEP_RENDER  what the kernel writes on any launch (the per-block loss, blast and wlast partials,
+//                the lanes' sink for masked-off stores), the band weights and the layer-0 column map;
+//   STEP_WARP    the dH partials, the loss partials, the lanes' sink and the band weights: nothing
+//                per pixel but the dH partials' 36 B per 32 slots.  Never pipelined.
+// A region a kind lacks is empty, at the offset where it would lie.
+static void plan_step2_bufs(const marf_net* n, const GeoDev& g, StepKind kind, Step2BufPlan& p) {
     const Step2NetPlan& q = n->s2;
     const int nl = n->n_layers;
-    const long long Ssave = render ? 0 : 1;
+    const bool full = kind == STEP_FULL, render = kind == STEP_RENDER, warp = kind == STEP_WARP;
+    memset(&p, 0, sizeof(p));
     p.S = (long long)g.B * g.Np_pad;
     p.n_tiles = (int)(p.S / q.TPX);
+    // the persistent grid: a block per CU at the most, or the pipeline's G
     int cap = device_cus();
     if (const char* e = getenv("MARF_STEP2_GRID")) cap = std::max(1, atoi(e));  // diagnostic override
     p.grid = std::max(1, std::min(p.n_tiles, cap));
-    memset(&p.pipe, 0, sizeof(p.pipe));
-    p.fused_res = false;
-    if (!render) plan_pipe(n, g, p.S, p.n_tiles, p.pipe);
+    if (full) plan_pipe(n, g, p.S, p.n_tiles, p.pipe);
     if (p.pipe.on) p.grid = p.pipe.G;
     p.nblk = p.pipe.on ? p.pipe.P * p.pipe.G : p.grid;
-    size_t off = 0;
+    Layout at;
+    auto region = [&at](bool has, long long bytes) { return at.take(has ? bytes : 0); };
     // (fp16x2: feat_l carries the 32 NW sink rows too -- a group's missing second set runs its
     //  forward and stores there)
     const long long Sfeat = p.S + (q.variant == 3 ? q.TPX : 0);
-    for (int l = 0; l < nl - 1; ++l) {
-        p.feat[l] = off;
-        off += rup(Ssave * Sfeat * (l == 0 ? q.ldf0 : n->Kp[l]) * 2, 256);
-    }
-    p.dz[0] = 0;
+    for (int l = 0; l < nl - 1; ++l) p.feat[l] = region(full, Sfeat * (l == 0 ? q.ldf0 : n->Kp[l]) * 2);
     // dz_l and the dH partials carry 32 NW sink rows past S: the dgrad pass of a pixel set that has
     // no tile (an odd tile count with two sets per dgrad pass) stores there
     const long long Ssink = p.S + q.TPX;
-    p.dzl = !render && dzl_recompute(n, g, p.S, p.pipe.on != 0);
-    for (int l = 1; l < nl; ++l) {
-        p.dz[l] = off;
-        if (p.dzl && l == nl - 1) continue;  // (recomputed: never stored)
-        off += rup(Ssave * Ssink * n->Kp[l] * 2, 256);
-    }
-    p.dzl_g = p.dzl_mk = p.dzl_w = 0;
-    if (p.dzl) {  // per 32-pixel set, the sink sets included
-        p.dzl_g = off;
-        off += rup(Ssink / 32 * DZL_G_SET, 256);
-        p.dzl_mk = off;
-        off += rup(Ssink / 32 * DZL_MK_SET, 256);
-        p.dzl_w = off;
-        off += DZL_W_BYTES;
-    }
-    p.dH = off;
-    off += rup(Ssave * Ssink / q.PX * 9 * 4, 256);
-    p.loss = off;
-    off += rup((long long)p.nblk * 2 * 8, 256);
-    p.blast = off;
-    off += rup((long long)p.nblk * 3 * 4, 256);
-    p.wlast = off;
-    off += rup((long long)p.nblk * 3 * q.Kl * 4, 256);
-    p.dummy = off;
-    off += rup((long long)p.grid * q.NW * 4096, 256);  // 64 B per lane
-    p.c2f = off;
-    off += 256;
-    p.kmap = off;  // the layer-0 column map, copied from the packed buffer by the forward
-    off += rup((long long)n->D * 4, 256);
+    p.dzl = full && dzl_recompute(n, g, p.S, p.pipe.on != 0);
+    for (int l = 1; l < nl; ++l)  // (dz_{n-1} recomputed: never stored)
+        p.dz[l] = region(full && !(p.dzl && l == nl - 1), Ssink * n->Kp[l] * 2);
+    // what takes dz_{n-1}'s place: per 32-pixel set, the sink sets included
+    p.dzl_g = region(p.dzl, Ssink / 32 * DZL_G_SET);
+    p.dzl_mk = region(p.dzl, Ssink / 32 * DZL_MK_SET);
+    p.dzl_w = region(p.dzl, DZL_W_BYTES);
+    p.dH = region(!render, Ssink / q.PX * 9 * 4);
+    p.loss = at.take((long long)p.nblk * 2 * 8);
+    p.blast = region(!warp, (long long)p.nblk * 3 * 4);
+    p.wlast = region(!warp, (long long)p.nblk * 3 * q.Kl * 4);
+    p.dummy = at.take((long long)p.grid * q.NW * 4096);  // 64 B per lane
+    p.c2f = at.take(256);
+    p.kmap = region(!warp, (long long)n->D * 4);  // the layer-0 column map, copied from the packed buffer by the forward
     // split-K partials of the hidden / layer-0 weight gradients (as plan_step)
-    long long chunk = rup((p.S + 255) / 256, 64);
-    if (chunk < 64) chunk = 64;
-    const long long n_chunks = (p.S + chunk - 1) / chunk;
-    long long mxo = 0, mxm = 0;
-    for (int l = 0; l < nl - 1; ++l) {
-        mxo = std::max(mxo, (long long)n->Mp[l] * (l == 0 ? q.ldf0 : n->Kp[l]));
-        mxm = std::max(mxm, (long long)n->Mp[l]);
-    }
+    p.k = split_k(p.S, 256);
+    long long mxo, mxm;
+    max_partial(*n, q.ldf0, mxo, mxm);
     if (p.pipe.on) {  // every layer's partials live from the forward to the backward's reduction
         const long long np = p.pipe.n_parts;
         for (int l = 0; l < nl - 1; ++l) {
-            p.partl[l] = off;
-            off += rup(np * n->Mp[l] * (l == 0 ? q.ldf0 : n->Kp[l]) * 4, 256);
-            p.bpartl[l] = off;
-            off += rup(np * n->Mp[l] * 4, 256);
+            p.partl[l] = at.take(np * n->Mp[l] * (l == 0 ? q.ldf0 : n->Kp[l]) * 4);
+            p.bpartl[l] = at.take(np * n->Mp[l] * 4);
         }
-        p.part = off;  // the fold scratch of the last-layer reduction
-        off += rup(256LL * (3 * q.Kl + 3) * 4, 256);
-        p.bpart = 0;
+        p.part = at.take(256LL * (3 * q.Kl + 3) * 4);  // the fold scratch of the last-layer reduction
     } else {
-        p.part = off;
-        off += rup(Ssave * std::max(n_chunks * mxo, 256LL * (3 * q.Kl + 3)) * 4, 256);
-        p.bpart = off;
-        off += rup(Ssave * n_chunks * mxm * 4, 256);
+        p.part = region(full, std::max(p.k.n * mxo, 256LL * (3 * q.Kl + 3)) * 4);
+        p.bpart = region(full, p.k.n * mxm * 4);
         // the fused weight gradients keep every layer's partials at once (layer 0: part); the
         // per-layer path reuses part / bpart for every layer, so nothing more is reserved for it
-        p.fused_res = !render && step2_fused_wgrad_possible(n);
+        p.fused_res = full && step2_fused_wgrad_possible(n);
         p.partl[0] = p.part;
         p.bpartl[0] = p.bpart;
         for (int l = 1; l < nl - 1; ++l) {
-            p.partl[l] = p.part;
-            p.bpartl[l] = p.bpart;
-            if (!p.fused_res) continue;
-            p.partl[l] = off;
-            off += rup(Ssave * n_chunks * n->Mp[l] * n->Kp[l] * 4, 256);
-            p.bpartl[l] = off;
-            off += rup(Ssave * n_chunks * n->Mp[l] * 4, 256);
+            p.partl[l] = p.fused_res ? at.take((long long)p.k.n * n->Mp[l] * n->Kp[l] * 4) : p.part;
+            p.bpartl[l] = p.fused_res ? at.take((long long)p.k.n * n->Mp[l] * 4) : p.bpart;
         }
     }
-    p.total = off;
+    p.total = at.off;
 }
 
 // the weight-gradient launches of piece j of a pipelined step (second stream)
@@ -1203,73 +1205,57 @@ static const char* warp_step_refusal(const marf_net* n) {
     return nullptr;
 }
 
-// The warp-only step's buffer on the pixel-per-wave kernel: the dH partials (with the sink rows of a
-// group's missing second pixel set), the per-block loss partials, the lanes' sink for masked-off
-// stores and the band weights.  Nothing per pixel but the dH partials' 36 B per 32 slots.  The grid as
-// plan_step2_bufs chooses it (MARF_STEP2_GRID included), never pipelined.
-static void plan_warp2_bufs(const marf_net* n, const GeoDev& g, Step2BufPlan& p) {
-    const Step2NetPlan& q = n->s2;
-    memset(&p, 0, sizeof(p));
-    p.S = (long long)g.B * g.Np_pad;
-    p.n_tiles = (int)(p.S / q.TPX);
-    int cap = device_cus();
-    if (const char* e = getenv("MARF_STEP2_GRID")) cap = std::max(1, atoi(e));  // diagnostic override
-    p.grid = std::max(1, std::min(p.n_tiles, cap));
-    p.nblk = p.grid;
-    size_t off = 0;
-    p.dH = off;
-    off += rup((p.S + q.TPX) / q.PX * 9 * 4, 256);
-    p.loss = off;
-    off += rup((long long)p.nblk * 2 * 8, 256);
-    p.dummy = off;
-    off += rup((long long)p.grid * q.NW * 4096, 256);  // 64 B per lane
-    p.c2f = off;
-    off += 256;
-    p.total = off;
-}
-
-// The same on the tile kernels: the ReLU records (the kernel's own dgrad re-reads them), the per-tile
-// dH and loss partials and the band weights.
-static void plan_warp_tile(const marf_net* n, long long S, StepPlan& p) {
-    memset(&p, 0, sizeof(p));
-    size_t off = 0;
-    p.n_tiles = (int)(S / n->sTP);
-    for (int l = 1; l < n->n_layers; ++l) {
-        p.mask[l] = off;
-        off += rup(S / n->sTP * n->sNW * 1024, 256);  // one uint4 per lane per wave per tile
+// The plan of a step's buffer, whichever kernel family runs the net: the geometry padded to the
+// family's tile, the family's plan (p2: k_step2 and its siblings; pt: the tile kernels) and where
+// the warp gradient finds its partials.  The byte-count entries and the backwards go through it.
+struct StepBufs {
+    GeoDev g;
+    Step2BufPlan p2;
+    StepPlan pt;
+    size_t total, dH;
+    int dH_per_patch;
+};
+static int plan_step_bufs(const marf_net* net, const marf_geometry* geo, StepKind kind, StepBufs& b) {
+    const bool s2 = use_step2(net);
+    int rc = make_geo(geo, b.g, s2 ? net->s2.TPX : MARF_TILE_PAD);
+    if (rc) return rc;
+    if (s2) {
+        plan_step2_bufs(net, b.g, kind, b.p2);
+        b.total = b.p2.total;
+        b.dH = b.p2.dH;
+        b.dH_per_patch = b.g.Np_pad / net->s2.PX;
+    } else {
+        plan_step(net, (long long)b.g.B * b.g.Np_pad, kind, b.pt);
+        b.total = b.pt.total;
+        b.dH = b.pt.dH;
+        b.dH_per_patch = b.g.Np_pad / net->sTP;
     }
-    p.dH = off;
-    off += rup((long long)p.n_tiles * 9 * 4, 256);
-    p.loss = off;
-    off += rup((long long)p.n_tiles * 2 * 8, 256);
-    p.c2f = off;
-    off += 256;
-    p.total = off;
+    return MARF_OK;
 }
 
-static hipError_t launch_s2(const marf_net* n, const Step2Args& a, int grid, hipStream_t s, bool warp = false) {
+static hipError_t launch_s2(const marf_net* n, const Step2Args& a, int grid, hipStream_t s, StepKind kind) {
     const Step2NetPlan& q = n->s2;
     // the compile-time layer-0 instantiations: split recipe, every hidden layer 256 wide, the
     // layer-0 row tiles per stage the kernel derives from nk0, a 256-wide last-layer input
     bool full = (q.variant == 1 || q.variant == 3) && q.nk0 >= 1 && q.r0 == std::max(1, std::min(8, 16 / q.nk0)) && q.Kl == 256;
     for (int l = 0; l < n->n_layers - 1; ++l) full = full && n->Mp[l] == 256;
     if (const char* e = getenv("MARF_STEP2_GENERIC")) full = full && e[0] != '1';  // (A/B: the generic kernel)
-    if (warp) return marf_launch_step2_warp(a, grid, s, full ? q.nk0 : 0);
+    if (kind == STEP_WARP) return marf_launch_step2_warp(a, grid, s, full ? q.nk0 : 0);
     return marf_launch_step2(a, q.variant, grid, s, full ? q.nk0 : 0, q.dz);
 }
 
+// STEP_WARP: k_step2w, no saved tensor, no wlast / blast; STEP_RENDER: the program's forward prefix
 static int step2_forward(const marf_net* net, const marf_geometry* geo, const marf_c2f* c2f, const void* d_packed,
                          const float* d_gt, const float* d_mask, const float* d_denom_override, float* d_rgb,
-                         float* d_loss_out, void* d_saved, hipStream_t s, bool render = false, bool warp = false) {
-    // warp: the warp-only step (k_step2w on plan_warp2_bufs): no saved tensor, no wlast / blast
+                         float* d_loss_out, void* d_saved, hipStream_t s, StepKind kind) {
+    const bool full = kind == STEP_FULL, render = kind == STEP_RENDER, warp = kind == STEP_WARP;
     const Step2NetPlan& q = net->s2;
     Step2Args a;
     memset(&a, 0, sizeof(a));
     int rc = make_geo(geo, a.geo, q.TPX);
     if (rc) return rc;
     Step2BufPlan p;
-    if (warp) plan_warp2_bufs(net, a.geo, p);
-    else plan_step2_bufs(net, a.geo, p, render);
+    plan_step2_bufs(net, a.geo, kind, p);
     char* sv = (char*)d_saved;
     const char* pk = (const char*)d_packed;
     const int nl = net->n_layers;
@@ -1292,7 +1278,7 @@ static int step2_forward(const marf_net* net, const marf_geometry* geo, const ma
     }
     a.bias = (const float*)(pk + q.bias_off);
     a.nbias = q.nbias;
-    a.feat0_recompute = !render && !warp && l0_recompute(net, a.geo, p.S) ? 1 : 0;
+    a.feat0_recompute = full && l0_recompute(net, a.geo, p.S) ? 1 : 0;
     if (p.dzl) {
         a.dzl_g = sv + p.dzl_g;
         a.dzl_mk = sv + p.dzl_mk;
@@ -1308,8 +1294,8 @@ static int step2_forward(const marf_net* net, const marf_geometry* geo, const ma
         y.boff = q.boff[l];
         y.ldf = l == 0 ? q.ldf0 : net->Kp[l];
         y.ldz = net->Kp[l];
-        y.feat = l < nl - 1 && !render && !warp ? (u16*)(sv + p.feat[l]) : nullptr;
-        y.dz = l >= 1 && !render && !warp && !(p.dzl && l == nl - 1) ? (u16*)(sv + p.dz[l]) : nullptr;
+        y.feat = full && l < nl - 1 ? (u16*)(sv + p.feat[l]) : nullptr;
+        y.dz = full && l >= 1 && !(p.dzl && l == nl - 1) ? (u16*)(sv + p.dz[l]) : nullptr;
     }
     a.dH_partial = (float*)(sv + p.dH);
     a.loss_partial = (double*)(sv + p.loss);
@@ -1343,7 +1329,7 @@ static int step2_forward(const marf_net* net, const marf_geometry* geo, const ma
         HIPCHK(marf_launch_c2f_weights(cf, net->L, (float*)(sv + p.c2f), s), "warp_step_forward c2f");
         {
             MarfProfScope ps("mlp_step_warp", s);
-            HIPCHK(launch_s2(net, a, p.grid, s, true), "warp_step_forward step2");
+            HIPCHK(launch_s2(net, a, p.grid, s, kind), "warp_step_forward step2");
         }
         MarfProfScope ps("loss_final", s);
         HIPCHK(marf_launch_loss_final(a.loss_partial, p.nblk, d_loss_out, d_denom_override, s), "warp_step_forward loss");
@@ -1354,13 +1340,13 @@ static int step2_forward(const marf_net* net, const marf_geometry* geo, const ma
            "step_forward c2f / kmap");
     if (render) {
         MarfProfScope ps("mlp_fwd", s);
-        HIPCHK(launch_s2(net, a, p.grid, s), "render step2");
+        HIPCHK(launch_s2(net, a, p.grid, s, kind), "render step2");
         return MARF_OK;
     }
     double* const loss0 = a.loss_partial;
     if (!p.pipe.on) {
         MarfProfScope ps("mlp_step", s);
-        HIPCHK(launch_s2(net, a, p.grid, s), "step_forward step2");
+        HIPCHK(launch_s2(net, a, p.grid, s, kind), "step_forward step2");
     } else {
         // pieces of the step kernel on stream s, each followed by its weight gradients on s2
         const PipePlan& pp = p.pipe;
@@ -1378,7 +1364,7 @@ static int step2_forward(const marf_net* net, const marf_geometry* geo, const ma
             a.wlast_partial = wlast0 + (size_t)j * pp.G * 3 * q.Kl;
             {
                 MarfProfScope ps("mlp_step", s);
-                HIPCHK(launch_s2(net, a, pp.G, s), "step_forward step2 piece");
+                HIPCHK(launch_s2(net, a, pp.G, s, kind), "step_forward step2 piece");
             }
             HIPCHK(hipEventRecord(st->ev[j], s), "pipeline: record");
             HIPCHK(hipStreamWaitEvent(st->s2, st->ev[j], 0), "pipeline: wait");
@@ -1401,15 +1387,13 @@ static int mark_layer(const void* const* ev, int l, hipStream_t s) {
     return MARF_OK;
 }
 
-static int step2_backward(const marf_net* net, const marf_geometry* geo, const void* d_saved,
-                          const float* d_h_params, int lie_batch, const float* d_gout, const float* d_loss_out,
-                          float* d_dparams, float* d_dh, hipStream_t s, const void* const* ev) {
+static int step2_backward(const marf_net* net, const StepBufs& bufs, const void* d_saved, const float* d_h_params,
+                          int lie_batch, const float* d_gout, const float* d_loss_out, float* d_dparams, float* d_dh,
+                          hipStream_t s, const void* const* ev) {
     const Step2NetPlan& q = net->s2;
-    GeoDev g;
-    int rc = make_geo(geo, g, q.TPX);
-    if (rc) return rc;
-    Step2BufPlan p;
-    plan_step2_bufs(net, g, p);
+    const GeoDev& g = bufs.g;
+    const Step2BufPlan& p = bufs.p2;
+    int rc;
     const char* sv = (const char*)d_saved;
     float* part = (float*)(sv + p.part);
     float* bpart = (float*)(sv + p.bpart);
@@ -1424,9 +1408,8 @@ static int step2_backward(const marf_net* net, const marf_geometry* geo, const v
     // The fused weight gradients (marf_launch_wgrad_fused): the hidden layers in one launch, layer 0
     // beside it on the side stream, every reduction in one launch -- the same partials and sums as
     // the per-layer launches below (bit-identical).  The layer events follow it, in the per-layer order.
+    const int chunk = p.k.chunk, n_chunks = p.k.n;  // (pipeline off: the split the plan sized part / bpart by)
     if (d_dparams && !p.pipe.on && p.fused_res) {
-        const long long chunk = wgrad_chunk(p.S);
-        const int n_chunks = (int)((p.S + chunk - 1) / chunk);
         const int* kmap = (const int*)(sv + p.kmap);
         const bool f0 = l0_recompute(net, g, p.S);
         WgFusedLayer Lf[MARF_MAX_LAYERS];
@@ -1464,7 +1447,7 @@ static int step2_backward(const marf_net* net, const marf_geometry* geo, const v
             x.kmap = l == 0 ? kmap : nullptr;
             if (p.dzl && l == nl - 2) x.dzl = dzl_src;
         }
-        if (marf_wgrad_fused_ok(Lf, nf, p.S, (int)chunk, n_chunks, g.Np_pad, net->L)) {
+        if (marf_wgrad_fused_ok(Lf, nf, p.S, chunk, n_chunks, g.Np_pad, net->L)) {
             PipeStreams* st = nullptr;
             rc = pipe_streams(&st);
             if (rc) return rc;
@@ -1478,7 +1461,7 @@ static int step2_backward(const marf_net* net, const marf_geometry* geo, const v
                 }
                 {
                     MarfProfScope ps("wgrad_fused", s);
-                    HIPCHK(marf_launch_wgrad_fused(Lf, nf, p.S, (int)chunk, n_chunks, g, (const float*)(sv + p.c2f),
+                    HIPCHK(marf_launch_wgrad_fused(Lf, nf, p.S, chunk, n_chunks, g, (const float*)(sv + p.c2f),
                                                    net->L, q.nk0w, d_gout, denom, s, st->s2, st->ev[0], st->ev[1], sdt, post),
                            "step_backward fused weight gradients");
                 }
@@ -1487,10 +1470,9 @@ static int step2_backward(const marf_net* net, const marf_geometry* geo, const v
                     // backward) reads only the step kernel's partials and the upstream gradient: it
                     // follows layer 0 on the side stream (ahead of it, it would hold layer 0 back
                     // until the hidden layers free a CU) and runs beside the reductions
-                    MarfProfScope ps("warp_bwd_side", st->s2);
-                    HIPCHK(marf_launch_reduce_dH((const float*)(sv + p.dH), g.Np_pad / q.PX, g.B, d_h_params, nullptr,
-                                                 dh_side, lie_batch > 0 ? lie_batch : g.B, st->s2, d_gout, denom),
-                           "step_backward warp");
+                    rc = launch_warp_bwd((const float*)(sv + bufs.dH), bufs.dH_per_patch, g, d_h_params, dh_side, lie_batch,
+                                         st->s2, d_gout, denom, "warp_bwd_side", "step_backward warp");
+                    if (rc) return rc;
                     HIPCHK(hipEventRecord(st->ev[3], st->s2), "step_backward: join");
                 }
                 for (int l = nl - 1; l >= 0; --l) {  // (ahead of the warp gradient's join: the
@@ -1531,8 +1513,6 @@ static int step2_backward(const marf_net* net, const marf_geometry* geo, const v
             if (rc) return rc;
         }
     } else if (d_dparams) {
-        const long long chunk = wgrad_chunk(p.S);
-        const int n_chunks = (int)((p.S + chunk - 1) / chunk);
         const int* kmap = (const int*)(sv + p.kmap);
         const bool f0 = l0_recompute(net, g, p.S);
         for (int l = nl - 2; l >= 0; --l) {
@@ -1541,12 +1521,12 @@ static int step2_backward(const marf_net* net, const marf_geometry* geo, const v
                 MarfProfScope ps(l == 0 ? "wgrad_l0" : "wgrad_hidden", s);
                 if (l == 0 && f0)
                     HIPCHK(marf_launch_wgrad_l0_recompute(sv + p.dz[1], net->Kp[1], g, (const float*)(sv + p.c2f), net->L,
-                                                          q.nk0w, q.ldf0, p.S, net->Mp[0], (int)chunk, n_chunks, part, bpart, s,
+                                                          q.nk0w, q.ldf0, p.S, net->Mp[0], chunk, n_chunks, part, bpart, s,
                                                           nullptr, sdt),
                            "step_backward wgrad_l0 (feat_0 recomputed)");
                 else
                     HIPCHK(marf_launch_wgrad(sdt, sv + p.dz[l + 1], net->Kp[l + 1], sv + p.feat[l], K, p.S, net->Mp[l], K,
-                                             (int)chunk, n_chunks, part, bpart, s, nullptr, true,
+                                             chunk, n_chunks, part, bpart, s, nullptr, true,
                                              p.dzl && l == nl - 2 ? &dzl_src : nullptr),
                            "step_backward wgrad");
             }
@@ -1561,22 +1541,16 @@ static int step2_backward(const marf_net* net, const marf_geometry* geo, const v
             if (rc) return rc;
         }
     }
-    if (d_dh) {
-        MarfProfScope ps("warp_bwd", s);
-        HIPCHK(marf_launch_reduce_dH((const float*)(sv + p.dH), g.Np_pad / q.PX, g.B, d_h_params, nullptr, d_dh,
-                                     lie_batch > 0 ? lie_batch : g.B, s, d_gout, denom),
-               "step_backward warp");
-    }
+    if (d_dh)
+        return launch_warp_bwd((const float*)(sv + bufs.dH), bufs.dH_per_patch, g, d_h_params, d_dh, lie_batch, s, d_gout,
+                               denom, "warp_bwd", "step_backward warp");
     return MARF_OK;
 }
 
 size_t marf_render_workspace_bytes(const marf_net* net, const marf_geometry* geo) {
-    if (!net || !geo || !use_step2(net)) return 0;
-    GeoDev g;
-    if (make_geo(geo, g, net->s2.TPX) != MARF_OK) return 0;
-    Step2BufPlan p;
-    plan_step2_bufs(net, g, p, true);
-    return p.total;
+    StepBufs b;
+    if (!net || !geo || !use_step2(net) || plan_step_bufs(net, geo, STEP_RENDER, b) != MARF_OK) return 0;
+    return b.total;
 }
 
 int marf_render(const marf_net* net, const marf_geometry* geo, const marf_c2f* c2f, const void* d_packed, float* d_rgb,
@@ -1605,22 +1579,13 @@ int marf_render(const marf_net* net, const marf_geometry* geo, const marf_c2f* c
         if (geo->Np <= 0 || !geo->d_coords) return fail(MARF_ERR_INVALID, "render: coords geometry needs points");
     }
     return step2_forward(net, geo, c2f, d_packed, nullptr, nullptr, nullptr, d_rgb, nullptr, d_ws,
-                         (hipStream_t)stream, true);
+                         (hipStream_t)stream, STEP_RENDER);
 }
 
 size_t marf_step_saved_bytes(const marf_net* net, const marf_geometry* geo) {
-    GeoDev g;
-    if (!net || !geo || geo->mode == MARF_GEO_COORDS) return 0;
-    if (use_step2(net)) {
-        if (make_geo(geo, g, net->s2.TPX) != MARF_OK) return 0;
-        Step2BufPlan p2;
-        plan_step2_bufs(net, g, p2);
-        return p2.total;
-    }
-    if (make_geo(geo, g, MARF_TILE_PAD) != MARF_OK) return 0;
-    StepPlan p;
-    plan_step(net, (long long)g.B * g.Np_pad, p);
-    return p.total;
+    StepBufs b;
+    if (!net || !geo || geo->mode == MARF_GEO_COORDS || plan_step_bufs(net, geo, STEP_FULL, b) != MARF_OK) return 0;
+    return b.total;
 }
 
 // The tile kernels' fused step forward (k_mlp_step / k_mlp_step_split), full or warp-only: one geometry, one
@@ -1628,7 +1593,8 @@ size_t marf_step_saved_bytes(const marf_net* net, const marf_geometry* geo) {
 // partials, the c2f table: nothing for a weight gradient), in the instantiation and in its profile name.
 static int tile_step_forward(const marf_net* net, const marf_geometry* geo, const marf_c2f* c2f, const void* d_packed,
                              const float* d_gt, const float* d_mask, const float* d_denom_override, float* d_rgb,
-                             float* d_loss_out, void* d_saved, hipStream_t s, bool warp) {
+                             float* d_loss_out, void* d_saved, hipStream_t s, StepKind kind) {
+    const bool warp = kind == STEP_WARP;
     StepArgs a;
     memset(&a, 0, sizeof(a));
     int rc = make_geo(geo, a.geo, MARF_TILE_PAD);
@@ -1641,10 +1607,7 @@ static int tile_step_forward(const marf_net* net, const marf_geometry* geo, cons
     a.S = (long long)a.geo.B * a.geo.Np_pad;
     a.lda = net->lda;
     StepPlan p;
-    if (warp)
-        plan_warp_tile(net, a.S, p);
-    else
-        plan_step(net, a.S, p);
+    plan_step(net, a.S, kind, p);
     char* sv = (char*)d_saved;
     const int nl = net->n_layers;
     for (int l = 1; l < nl; ++l) a.mask_bits[l] = (uint64_t*)(sv + p.mask[l]);
@@ -1685,8 +1648,8 @@ int marf_step_forward(const marf_net* net, const marf_geometry* geo, const marf_
     if (!geo || geo->mode == MARF_GEO_COORDS) return fail(MARF_ERR_INVALID, "step_forward: needs a pixel-grid geometry");
     hipStream_t s = (hipStream_t)stream;
     if (use_step2(net))
-        return step2_forward(net, geo, c2f, d_packed, d_gt, d_mask, d_denom_override, d_rgb, d_loss_out, d_saved, s);
-    return tile_step_forward(net, geo, c2f, d_packed, d_gt, d_mask, d_denom_override, d_rgb, d_loss_out, d_saved, s, false);
+        return step2_forward(net, geo, c2f, d_packed, d_gt, d_mask, d_denom_override, d_rgb, d_loss_out, d_saved, s, STEP_FULL);
+    return tile_step_forward(net, geo, c2f, d_packed, d_gt, d_mask, d_denom_override, d_rgb, d_loss_out, d_saved, s, STEP_FULL);
 }
 
 int marf_step_backward(const marf_net* net, const marf_geometry* geo, const void* d_saved, const float* d_h_params,
@@ -1704,14 +1667,14 @@ int marf_step_backward_ev(const marf_net* net, const marf_geometry* geo, const v
     if (!geo || geo->mode == MARF_GEO_COORDS) return fail(MARF_ERR_INVALID, "step_backward: needs a pixel-grid geometry");
     if (d_dh && !d_h_params) return fail(MARF_ERR_INVALID, "step_backward: d_dh requested without the warp parameters");
     hipStream_t s = (hipStream_t)stream;
-    if (use_step2(net))
-        return step2_backward(net, geo, d_saved, d_h_params, lie_batch, d_gout, d_loss_out, d_dparams, d_dh, s, ev);
-    GeoDev g;
-    int rc = make_geo(geo, g, MARF_TILE_PAD);
+    StepBufs bufs;
+    int rc = plan_step_bufs(net, geo, STEP_FULL, bufs);
     if (rc) return rc;
+    if (use_step2(net))
+        return step2_backward(net, bufs, d_saved, d_h_params, lie_batch, d_gout, d_loss_out, d_dparams, d_dh, s, ev);
+    const GeoDev& g = bufs.g;
+    const StepPlan& p = bufs.pt;
     const long long S = (long long)g.B * g.Np_pad;
-    StepPlan p;
-    plan_step(net, S, p);
     const char* sv = (const char*)d_saved;
     float* part = (float*)(sv + p.part);
     float* bpart = (float*)(sv + p.bpart);
@@ -1732,12 +1695,12 @@ int marf_step_backward_ev(const marf_net* net, const marf_geometry* geo, const v
             {
                 MarfProfScope ps(l == 0 ? "wgrad_l0" : "wgrad_hidden", s);
                 HIPCHK(marf_launch_wgrad(net->kdt, sv + p.dz[l + 1], net->Kp[l + 1], sv + p.feat[l], net->Kp[l], S,
-                                         net->Mp[l], net->Kp[l], p.chunk, p.n_chunks, part, bpart, s),
+                                         net->Mp[l], net->Kp[l], p.k.chunk, p.k.n, part, bpart, s),
                        "step_backward wgrad");
             }
             {
                 MarfProfScope ps("wgrad_reduce", s);
-                HIPCHK(marf_launch_wgrad_reduce(part, bpart, p.n_chunks, net->Mp[l], net->Kp[l], net->dims[l + 1],
+                HIPCHK(marf_launch_wgrad_reduce(part, bpart, p.k.n, net->Mp[l], net->Kp[l], net->dims[l + 1],
                                                 net->kin[l], d_dparams + net->w_off[l], d_dparams + net->b_off[l], s,
                                                 d_gout, denom),
                        "step_backward wgrad reduce");
@@ -1746,34 +1709,23 @@ int marf_step_backward_ev(const marf_net* net, const marf_geometry* geo, const v
             if (rc) return rc;
         }
     }
-    if (d_dh) {
-        MarfProfScope ps("warp_bwd", s);
-        HIPCHK(marf_launch_reduce_dH((const float*)(sv + p.dH), g.Np_pad / net->sTP, g.B, d_h_params, nullptr, d_dh,
-                                     lie_batch > 0 ? lie_batch : g.B, s, d_gout, denom),
-               "step_backward warp");
-    }
+    if (d_dh)
+        return launch_warp_bwd((const float*)(sv + bufs.dH), bufs.dH_per_patch, g, d_h_params, d_dh, lie_batch, s, d_gout,
+                               denom, "warp_bwd", "step_backward warp");
     return MARF_OK;
 }
 
 // ---- the warp-only step: a frozen image registers further patches (include/marf.h)
 
 size_t marf_warp_step_saved_bytes(const marf_net* net, const marf_geometry* geo) {
-    GeoDev g;
     if (!net || !geo || geo->mode == MARF_GEO_COORDS) return 0;
     if (const char* why = warp_step_refusal(net)) {
         fail(MARF_ERR_UNSUPPORTED, "warp_step: %s", why);
         return 0;
     }
-    if (use_step2(net)) {
-        if (make_geo(geo, g, net->s2.TPX) != MARF_OK) return 0;
-        Step2BufPlan p2;
-        plan_warp2_bufs(net, g, p2);
-        return p2.total;
-    }
-    if (make_geo(geo, g, MARF_TILE_PAD) != MARF_OK) return 0;
-    StepPlan p;
-    plan_warp_tile(net, (long long)g.B * g.Np_pad, p);
-    return p.total;
+    StepBufs b;
+    if (plan_step_bufs(net, geo, STEP_WARP, b) != MARF_OK) return 0;
+    return b.total;
 }
 
 int marf_warp_step_forward(const marf_net* net, const marf_geometry* geo, const marf_c2f* c2f, const void* d_packed,
@@ -1784,9 +1736,8 @@ int marf_warp_step_forward(const marf_net* net, const marf_geometry* geo, const 
     if (const char* why = warp_step_refusal(net)) return fail(MARF_ERR_UNSUPPORTED, "warp_step_forward: %s", why);
     hipStream_t s = (hipStream_t)stream;
     if (use_step2(net))
-        return step2_forward(net, geo, c2f, d_packed, d_gt, d_mask, d_denom_override, d_rgb, d_loss_out, d_saved, s, false,
-                             true);
-    return tile_step_forward(net, geo, c2f, d_packed, d_gt, d_mask, d_denom_override, d_rgb, d_loss_out, d_saved, s, true);
+        return step2_forward(net, geo, c2f, d_packed, d_gt, d_mask, d_denom_override, d_rgb, d_loss_out, d_saved, s, STEP_WARP);
+    return tile_step_forward(net, geo, c2f, d_packed, d_gt, d_mask, d_denom_override, d_rgb, d_loss_out, d_saved, s, STEP_WARP);
 }
 
 // the fixed-order sum of the dH partials and the Lie backward, on the caller's stream alone
@@ -1796,32 +1747,11 @@ int marf_warp_step_backward(const marf_net* net, const marf_geometry* geo, const
         return fail(MARF_ERR_INVALID, "warp_step_backward: NULL argument");
     if (!geo || geo->mode == MARF_GEO_COORDS) return fail(MARF_ERR_INVALID, "warp_step_backward: needs a pixel-grid geometry");
     if (const char* why = warp_step_refusal(net)) return fail(MARF_ERR_UNSUPPORTED, "warp_step_backward: %s", why);
-    hipStream_t s = (hipStream_t)stream;
-    const char* sv = (const char*)d_saved;
-    const float* denom = d_loss_out + 1;
-    GeoDev g;
-    size_t dH;
-    int per_patch;
-    if (use_step2(net)) {
-        int rc = make_geo(geo, g, net->s2.TPX);
-        if (rc) return rc;
-        Step2BufPlan p;
-        plan_warp2_bufs(net, g, p);
-        dH = p.dH;
-        per_patch = g.Np_pad / net->s2.PX;
-    } else {
-        int rc = make_geo(geo, g, MARF_TILE_PAD);
-        if (rc) return rc;
-        StepPlan p;
-        plan_warp_tile(net, (long long)g.B * g.Np_pad, p);
-        dH = p.dH;
-        per_patch = g.Np_pad / net->sTP;
-    }
-    MarfProfScope ps("warp_bwd", s);
-    HIPCHK(marf_launch_reduce_dH((const float*)(sv + dH), per_patch, g.B, d_h_params, nullptr, d_dh,
-                                 lie_batch > 0 ? lie_batch : g.B, s, d_gout, denom),
-           "warp_step_backward warp");
-    return MARF_OK;
+    StepBufs b;
+    int rc = plan_step_bufs(net, geo, STEP_WARP, b);
+    if (rc) return rc;
+    return launch_warp_bwd((const float*)((const char*)d_saved + b.dH), b.dH_per_patch, b.g, d_h_params, d_dh, lie_batch,
+                           (hipStream_t)stream, d_gout, d_loss_out + 1, "warp_bwd", "warp_step_backward warp");
 }
 
 // ------------------------------------------------------------------ loss / optimizer
@@ -1863,72 +1793,13 @@ int marf_masked_mse_mask_backward(const float* d_pred, const float* d_gt, const 
 
 // ImplicitMask + PosEmbedding + embedding_view (model/planar.py:319-327, 475-518): shape and
 // padding plan of the per-pixel mask MLP, in the tile kernels' layouts (marf_common.h)
-struct marf_mask_net {
+// (its saved and workspace buffers: plan_saved and plan_ws, with no dH region)
+struct marf_mask_net : NetShape {
     // kdt: arithmetic of the generic weight-gradient launchers (0 fp32, 1 bf16); split: MARF_BF16X3A, every
     // operand and saved tensor as two bf16 planes (hi, lo) -- elem stays 4 bytes per stored value
-    int n_vocab, embed_dim, n_freqs, n_layers, dtype, kdt, elem, split;
-    int dims[MARF_MAX_LAYERS + 1];
-    int Kp[MARF_MAX_LAYERS], Mp[MARF_MAX_LAYERS], Mt[MARF_MAX_LAYERS];
-    long long w_off[MARF_MAX_LAYERS], b_off[MARF_MAX_LAYERS], param_count;
-    long long wf_off[MARF_MAX_LAYERS], wt_off[MARF_MAX_LAYERS], bias_off[MARF_MAX_LAYERS];
-    size_t packed_bytes, lds;
-    int TP, lda;
+    int n_vocab, embed_dim, n_freqs, dtype, split;
+    size_t lds;
 };
-
-struct MaskSavedPlan {
-    size_t feat[MARF_MAX_LAYERS], mask[MARF_MAX_LAYERS], total;
-};
-
-static void plan_mask_saved(const marf_mask_net* n, long long S, MaskSavedPlan& p) {
-    size_t off = 0;
-    for (int l = 0; l < n->n_layers; ++l) {
-        p.feat[l] = off;
-        off += rup((long long)S * n->Kp[l] * n->elem, 256);
-    }
-    p.mask[0] = 0;
-    for (int l = 1; l < n->n_layers; ++l) {
-        p.mask[l] = off;
-        off += rup(S / n->TP * 4096, 256);  // one uint4 per lane per wave per tile
-    }
-    p.total = off;
-}
-
-struct MaskWsPlan {
-    size_t dz[MARF_MAX_LAYERS], glast, part, bpart, total;
-    int chunk, n_chunks, chunk_last, n_chunks_last;
-};
-
-static void plan_mask_ws(const marf_mask_net* n, long long S, MaskWsPlan& p) {
-    size_t off = 0;
-    p.dz[0] = 0;
-    for (int l = 1; l < n->n_layers; ++l) {
-        p.dz[l] = off;
-        off += rup((long long)S * n->Kp[l] * n->elem, 256);
-    }
-    p.glast = off;
-    off += rup(S * 16, 256);
-    long long chunk = rup((S + 255) / 256, 64);
-    if (chunk < 64) chunk = 64;
-    p.chunk = (int)chunk;
-    p.n_chunks = (int)((S + chunk - 1) / chunk);
-    long long cl = rup((S + 1023) / 1024, 64);
-    if (cl < 64) cl = 64;
-    p.chunk_last = (int)cl;
-    p.n_chunks_last = (int)((S + cl - 1) / cl);
-    long long mxo = 0, mxm = 0;
-    for (int l = 0; l < n->n_layers - 1; ++l) {
-        mxo = std::max(mxo, (long long)n->Mp[l] * n->Kp[l]);
-        mxm = std::max(mxm, (long long)n->Mp[l]);
-    }
-    const long long part_elems =
-        std::max((long long)p.n_chunks * mxo, (long long)p.n_chunks_last * 3 * n->Kp[n->n_layers - 1]);
-    const long long bpart_elems = std::max((long long)p.n_chunks * mxm, (long long)p.n_chunks_last * 3);
-    p.part = off;
-    off += rup(part_elems * 4, 256);
-    p.bpart = off;
-    off += rup(bpart_elems * 4, 256);
-    p.total = off;
-}
 
 // the mask net's pixel slots: the crop (or canvas) grid of the step, no homographies needed
 static int make_mask_geo(const marf_geometry* geo, GeoDev& d) {
@@ -1941,21 +1812,6 @@ static int make_mask_geo(const marf_geometry* geo, GeoDev& d) {
     const int rc = make_geo(&g, d, MARF_TILE_PAD);
     d.Hm = nullptr;
     return rc;
-}
-
-static void fill_mask_netdev(const marf_mask_net* n, const void* packed, NetDev& d) {
-    memset(&d, 0, sizeof(d));
-    d.n_layers = n->n_layers;
-    d.L = n->n_freqs;
-    d.D = n->dims[0];
-    for (int l = 0; l < n->n_layers; ++l) {
-        d.Kp[l] = n->Kp[l];
-        d.Mp[l] = n->Mp[l];
-        d.Mt[l] = n->Mt[l];
-        d.Wf[l] = (const char*)packed + n->wf_off[l];
-        d.Wt[l] = (const char*)packed + n->wt_off[l];
-        d.bias[l] = (const float*)((const char*)packed + n->bias_off[l]);
-    }
 }
 
 extern "C" {
@@ -1994,6 +1850,7 @@ int marf_mask_net_create(int n_vocab, int embed_dim, int n_freqs, int width, int
     n->dims[0] = D;
     for (int l = 1; l < n_layers; ++l) n->dims[l] = width;
     n->dims[n_layers] = 1;
+    for (int l = 0; l < n_layers; ++l) n->kin[l] = n->dims[l];
     n->Kp[0] = (int)rup(D, 32);
     for (int l = 0; l < n_layers - 1; ++l) {
         n->Mp[l] = width;
@@ -2010,22 +1867,7 @@ int marf_mask_net_create(int n_vocab, int embed_dim, int n_freqs, int width, int
         delete n;
         return fail(MARF_ERR_UNSUPPORTED, "mask_net_create: tile does not fit LDS (%zu B)", n->lds);
     }
-    long long off = 0;
-    size_t boff = 0;
-    for (int l = 0; l < n_layers; ++l) {
-        n->w_off[l] = off;
-        off += (long long)n->dims[l + 1] * n->dims[l];
-        n->b_off[l] = off;
-        off += n->dims[l + 1];
-        n->wf_off[l] = (long long)boff;
-        boff += rup((long long)n->Mp[l] * n->Kp[l] * n->elem, 256);
-        n->wt_off[l] = (long long)boff;
-        boff += rup((long long)n->Kp[l] * n->Mt[l] * n->elem, 256);
-        n->bias_off[l] = (long long)boff;
-        boff += rup((long long)n->Mp[l] * 4, 256);
-    }
-    n->param_count = off;
-    n->packed_bytes = boff;
+    plan_params(*n, n->elem);
     *out = n;
     return MARF_OK;
 }
@@ -2037,23 +1879,7 @@ size_t marf_mask_net_packed_bytes(const marf_mask_net* net) { return net ? net->
 int marf_mask_net_pack(const marf_mask_net* net, const float* d_params, void* d_packed, void* stream) {
     if (!net || !d_params || !d_packed) return fail(MARF_ERR_INVALID, "mask_net_pack: NULL argument");
     PackArgs a;
-    memset(&a, 0, sizeof(a));
-    a.n_layers = net->n_layers;
-    long long mx = 0;
-    for (int l = 0; l < net->n_layers; ++l) {
-        PackLayer& p = a.ly[l];
-        p.M = net->dims[l + 1];
-        p.K = net->dims[l];
-        p.Mp = net->Mp[l];
-        p.Kp = net->Kp[l];
-        p.Mt = net->Mt[l];
-        p.w_off = net->w_off[l];
-        p.b_off = net->b_off[l];
-        p.wf_off = net->wf_off[l];
-        p.wt_off = net->wt_off[l];
-        p.bias_off = net->bias_off[l];
-        mx = std::max(mx, (long long)p.Mp * p.Kp + (long long)p.Kp * p.Mt + p.Mp);
-    }
+    const long long mx = fill_pack_args(*net, a);
     MarfProfScope ps("mask_pack_weights", (hipStream_t)stream);
     HIPCHK(marf_launch_pack(net->split ? 3 : net->kdt, d_params, (char*)d_packed, a, mx, (hipStream_t)stream), "mask_net_pack");
     return MARF_OK;
@@ -2062,16 +1888,16 @@ int marf_mask_net_pack(const marf_mask_net* net, const float* d_params, void* d_
 size_t marf_mask_saved_bytes(const marf_mask_net* net, const marf_geometry* geo) {
     GeoDev g;
     if (!net || make_mask_geo(geo, g) != MARF_OK) return 0;
-    MaskSavedPlan p;
-    plan_mask_saved(net, (long long)g.B * g.Np_pad, p);
+    SavedPlan p;
+    plan_saved(*net, (long long)g.B * g.Np_pad, p);
     return p.total;
 }
 
 size_t marf_mask_workspace_bytes(const marf_mask_net* net, const marf_geometry* geo) {
     GeoDev g;
     if (!net || make_mask_geo(geo, g) != MARF_OK) return 0;
-    MaskWsPlan p;
-    plan_mask_ws(net, (long long)g.B * g.Np_pad, p);
+    WsPlan p;
+    plan_ws(*net, (long long)g.B * g.Np_pad, 0, p);
     return p.total;
 }
 
@@ -2082,7 +1908,7 @@ int marf_mask_forward(const marf_mask_net* net, const marf_geometry* geo, const 
     memset(&a, 0, sizeof(a));
     int rc = make_mask_geo(geo, a.geo);
     if (rc) return rc;
-    fill_mask_netdev(net, d_packed, a.net);
+    fill_netdev(*net, net->n_freqs, d_packed, a.net);
     a.embed = d_embed;
     a.index = d_index;
     a.n_vocab = net->n_vocab;
@@ -2093,8 +1919,8 @@ int marf_mask_forward(const marf_mask_net* net, const marf_geometry* geo, const 
     a.split = net->split;
     const long long S = (long long)a.geo.B * a.geo.Np_pad;
     if (d_saved) {
-        MaskSavedPlan p;
-        plan_mask_saved(net, S, p);
+        SavedPlan p;
+        plan_saved(*net, S, p);
         for (int l = 0; l < net->n_layers; ++l) a.feat[l] = (char*)d_saved + p.feat[l];
         for (int l = 1; l < net->n_layers; ++l) a.mask[l] = (uint64_t*)((char*)d_saved + p.mask[l]);
     }
@@ -2112,16 +1938,16 @@ int marf_mask_backward(const marf_mask_net* net, const marf_geometry* geo, const
     memset(&a, 0, sizeof(a));
     int rc = make_mask_geo(geo, a.geo);
     if (rc) return rc;
-    fill_mask_netdev(net, d_packed, a.net);
+    fill_netdev(*net, net->n_freqs, d_packed, a.net);
     a.m = d_m;
     a.dm = d_dm;
     a.lda = net->lda;
     a.split = net->split;
     const long long S = (long long)a.geo.B * a.geo.Np_pad;
-    MaskSavedPlan sp;
-    plan_mask_saved(net, S, sp);
-    MaskWsPlan wp;
-    plan_mask_ws(net, S, wp);
+    SavedPlan sp;
+    plan_saved(*net, S, sp);
+    WsPlan wp;
+    plan_ws(*net, S, 0, wp);
     char* ws = (char*)d_workspace;
     const char* sv = (const char*)d_saved;
     for (int l = 1; l < net->n_layers; ++l) {
@@ -2145,16 +1971,16 @@ int marf_mask_backward(const marf_mask_net* net, const marf_geometry* geo, const
                 const char* ftp = sv + sp.feat[l];
                 HIPCHK(marf_launch_wgrad_split(dzp, dzp + (size_t)S * net->Kp[l + 1] * 2, net->Kp[l + 1], ftp,
                                                ftp + (size_t)S * net->Kp[l] * 2, net->Kp[l], S, net->Mp[l], net->Kp[l],
-                                               wp.chunk, wp.n_chunks, part, bpart, s),
+                                               wp.k.chunk, wp.k.n, part, bpart, s),
                        "mask_backward wgrad");
             } else {
                 HIPCHK(marf_launch_wgrad(net->kdt, ws + wp.dz[l + 1], net->Kp[l + 1], sv + sp.feat[l], net->Kp[l], S,
-                                         net->Mp[l], net->Kp[l], wp.chunk, wp.n_chunks, part, bpart, s),
+                                         net->Mp[l], net->Kp[l], wp.k.chunk, wp.k.n, part, bpart, s),
                        "mask_backward wgrad");
             }
         }
         MarfProfScope ps("mask_wgrad_reduce", s);
-        HIPCHK(marf_launch_wgrad_reduce(part, bpart, wp.n_chunks, net->Mp[l], net->Kp[l], net->dims[l + 1],
+        HIPCHK(marf_launch_wgrad_reduce(part, bpart, wp.k.n, net->Mp[l], net->Kp[l], net->dims[l + 1],
                                         net->dims[l], d_dparams + net->w_off[l], d_dparams + net->b_off[l], s),
                "mask_backward wgrad reduce");
     }
@@ -2162,12 +1988,12 @@ int marf_mask_backward(const marf_mask_net* net, const marf_geometry* geo, const
     {
         MarfProfScope ps("mask_wgrad_last", s);
         // (split: feat_{n-1} was saved as fp32, float(hi) + float(lo): the fp32 kernel serves both recipes)
-        HIPCHK(marf_launch_wgrad_last(0, a.glast, sv + sp.feat[l], S, net->Kp[l], net->Kp[l], wp.chunk_last,
-                                      wp.n_chunks_last, part, bpart, s),
+        HIPCHK(marf_launch_wgrad_last(0, a.glast, sv + sp.feat[l], S, net->Kp[l], net->Kp[l], wp.k_last.chunk,
+                                      wp.k_last.n, part, bpart, s),
                "mask_backward wgrad last");
     }
     // glast rows 1..3 are zero: row 0 of the 3-row partial is the one real output row
-    HIPCHK(marf_launch_wgrad_reduce(part, bpart, wp.n_chunks_last, 3, net->Kp[l], 1, net->dims[l],
+    HIPCHK(marf_launch_wgrad_reduce(part, bpart, wp.k_last.n, 3, net->Kp[l], 1, net->dims[l],
                                     d_dparams + net->w_off[l], d_dparams + net->b_off[l], s),
            "mask_backward wgrad last reduce");
     return MARF_OK;
