@@ -98,6 +98,30 @@ struct NetShape {
     int TP, lda;
 };
 
+// The weight gradient of layer l as the net's shape gives it: dz_{l+1} [S][Kp[l+1]] (x) feat_l
+// [S][Kp[l]] in the kernels' arithmetic, split over the pixel rows by k.  A site adds what is its
+// own: its pointers, the tensors' layout, a recomputed operand, a range.
+static WgShape wg_shape(const NetShape& n, int l, long long S, SplitK k) {
+    WgShape w = {};
+    w.dtype = n.kdt;
+    w.M = n.Mp[l];
+    w.ldz = n.Kp[l + 1];
+    w.K = w.ldf = n.Kp[l];
+    w.S = S;
+    w.chunk = k.chunk;
+    w.n_chunks = k.n;
+    return w;
+}
+static WgJob wg_job(const WgShape& w, const void* dz, const void* feat, float* partial, float* bpartial) {
+    WgJob j = {};
+    static_cast<WgShape&>(j) = w;
+    j.dz = dz;
+    j.feat = feat;
+    j.partial = partial;
+    j.bpartial = bpartial;
+    return j;
+}
+
 // W_l then b_l in the flat parameter vector; Wf_l, Wt_l, bias_l in the packed buffer (pelem: bytes
 // per packed weight).  dims, kin, Kp, Mp, Mt are set.
 static void plan_params(NetShape& n, int pelem) {
@@ -855,8 +879,7 @@ int marf_backward(const marf_net* net, const marf_geometry* geo, const marf_c2f*
         for (int l = 0; l < nl - 1; ++l) {
             {
                 MarfProfScope ps(l == 0 ? "wgrad_l0" : "wgrad_hidden", s);
-                HIPCHK(marf_launch_wgrad(net->kdt, ws + wp.dz[l + 1], net->Kp[l + 1], sv + sp.feat[l], net->Kp[l],
-                                         a.S, net->Mp[l], net->Kp[l], wp.k.chunk, wp.k.n, part, bpart, s),
+                HIPCHK(marf_launch_wgrad(wg_job(wg_shape(*net, l, a.S, wp.k), ws + wp.dz[l + 1], sv + sp.feat[l], part, bpart), s),
                        "backward wgrad");
             }
             {
@@ -986,14 +1009,26 @@ static int device_cus() {
 
 static bool use_step2(const marf_net* n) { return n->s2.variant >= 0; }
 
+// ... of the pixel-per-wave step: its saved tensors (T16; fp16 for fp16x2), layer 0 ldf0 wide
+static WgShape step2_wg_shape(const marf_net* n, const GeoDev& g, int l, long long S, SplitK k) {
+    WgShape w = wg_shape(*n, l, S, k);
+    w.dtype = n->s2.variant == 3 ? 2 : 1;
+    if (l == 0) w.K = w.ldf = n->s2.ldf0;
+    w.t16 = true;
+    w.L = n->L;  // (read when feat_0 is recomputed)
+    w.Np_pad = g.Np_pad;
+    return w;
+}
+
 // The layer-0 weight gradient recomputes feat_0 (grid -> warp -> posenc + c2f, bf16 hi) instead of
 // reading it, so the step kernel does not store it (MARF_F0_RECOMPUTE=0: store and read, for A/B).
 static bool l0_recompute(const marf_net* n, const GeoDev& g, long long S) {
     const char* e = getenv("MARF_F0_RECOMPUTE");
     if (e && e[0] == '0') return false;
     if ((n->s2.variant != 1 && n->s2.variant != 3) || g.mode != MARF_GEO_GRID) return false;
-    const SplitK k = split_k(S, 256);
-    return marf_wgrad_l0_recompute_ok(n->Mp[0], n->Kp[1], n->s2.ldf0, n->L, S, k.chunk, k.n, g.Np_pad);
+    WgShape w = step2_wg_shape(n, g, 0, S, split_k(S, 256));
+    w.f0 = true;
+    return marf_wgrad_pick(w).k == WG_DMA_F0;
 }
 
 // The weight gradient of the last hidden layer (n-2) recomputes dz_{n-1} = relu'(z) (W_{n-1}^T g), a
@@ -1010,8 +1045,9 @@ static bool dzl_recompute(const marf_net* n, const GeoDev& g, long long S, bool 
     if (n->s2.variant != 1 || n->s2.dz || pipe_on || g.mode != MARF_GEO_GRID || nl < 3 || n->s2.NMW != 4) return false;
     for (int l = 0; l < nl - 1; ++l)
         if (n->Mp[l] != 256 || (l > 0 && n->Kp[l] != 256)) return false;
-    const SplitK k = split_k(S, 256);
-    return marf_wgrad_dzl_ok(n->Mp[nl - 2], n->Kp[nl - 1], n->Kp[nl - 2], n->Kp[nl - 2], S, k.chunk, k.n);
+    WgShape w = step2_wg_shape(n, g, nl - 2, S, split_k(S, 256));
+    w.dzl = true;
+    return marf_wgrad_pick(w).k == WG_DMA_DZL;
 }
 
 // ---- pipelined weight gradients (large steps of the pixel-per-wave kernel)
@@ -1052,12 +1088,16 @@ static void plan_pipe(const marf_net* n, const GeoDev& g, long long S, int n_til
     if (P > MARF_PIPE_MAXP) return;
     // every weight gradient on the range-capable LDS-DMA kernel
     const int nl = n->n_layers;
-    for (int l = 1; l < nl - 1; ++l)
-        if (!marf_wgrad_range_ok(n->kdt, n->Mp[l], n->Kp[l + 1], n->Kp[l], n->Kp[l])) return;
-    if (!marf_wgrad_range_ok(n->kdt, n->Mp[0], n->Kp[1], q.ldf0, q.ldf0)) return;
+    for (int l = 0; l < nl - 1; ++l) {
+        WgShape w = step2_wg_shape(n, g, l, S, {0, cus});
+        w.ranged = true;
+        if (marf_wgrad_pick(w).k == WG_NONE) return;
+    }
     if (l0_recompute(n, g, S)) {  // the recomputing kernel's ranges may span only a few patches
         const long long mx = rup((long long)piece * q.TPX / R + 32, 32);
-        if (!marf_wgrad_l0_recompute_ok(n->Mp[0], n->Kp[1], q.ldf0, n->L, S, (int)mx, P * cus, g.Np_pad)) return;
+        WgShape w = step2_wg_shape(n, g, 0, S, {(int)mx, P * cus});
+        w.f0 = true;
+        if (marf_wgrad_pick(w).k != WG_DMA_F0) return;
     }
     pp.on = 1;
     pp.G = G;
@@ -1163,6 +1203,24 @@ static void plan_step2_bufs(const marf_net* n, const GeoDev& g, StepKind kind, S
     p.total = at.off;
 }
 
+// layer l's weight gradient from what the step kernel saved: feat_0 / dz_{n-1} recomputed where
+// the buffer plan says the step kernel did not store them
+static WgJob step2_wg_job(const marf_net* net, const GeoDev& g, const Step2BufPlan& p, const char* sv, int l, SplitK k,
+                          float* partial, float* bpartial, bool f0) {
+    WgJob j = wg_job(step2_wg_shape(net, g, l, p.S, k), sv + p.dz[l + 1], sv + p.feat[l], partial, bpartial);
+    if (l == 0 && f0) {
+        j.f0 = true;
+        j.f0_geo = &g;
+        j.c2f_w = (const float*)(sv + p.c2f);
+        j.nk0 = net->s2.nk0w;
+    }
+    if (p.dzl && l == net->n_layers - 2) {
+        j.dzl = true;
+        j.dzl_src = {sv + p.dzl_g, sv + p.dzl_mk, sv + p.dzl_w};
+    }
+    return j;
+}
+
 // the weight-gradient launches of piece j of a pipelined step (second stream)
 static int wgrad_piece(const marf_net* net, const GeoDev& g, const Step2BufPlan& p, char* sv, int j, hipStream_t s2) {
     const Step2NetPlan& q = net->s2;
@@ -1177,18 +1235,11 @@ static int wgrad_piece(const marf_net* net, const GeoDev& g, const Step2BufPlan&
     r.part0 = j * pp.R;
     const bool f0 = l0_recompute(net, g, p.S);
     for (int l = 0; l < nl - 1; ++l) {
-        const int K = l == 0 ? q.ldf0 : net->Kp[l];
-        float* part = (float*)(sv + p.partl[l]);
-        float* bpart = (float*)(sv + p.bpartl[l]);
+        WgJob w = step2_wg_job(net, g, p, sv, l, {0, r.n}, (float*)(sv + p.partl[l]), (float*)(sv + p.bpartl[l]), f0);
+        w.ranged = true;
+        w.rng = r;
         MarfProfScope ps(l == 0 ? "wgrad_l0" : "wgrad_hidden", s2);
-        if (l == 0 && f0)
-            HIPCHK(marf_launch_wgrad_l0_recompute(sv + p.dz[1], net->Kp[1], g, (const float*)(sv + p.c2f), net->L, q.nk0w,
-                                                  q.ldf0, p.S, net->Mp[0], 32, r.n, part, bpart, s2, &r),
-                   "step_forward pipelined wgrad_l0");
-        else
-            HIPCHK(marf_launch_wgrad(1, sv + p.dz[l + 1], net->Kp[l + 1], sv + p.feat[l], K, p.S, net->Mp[l], K, 32, r.n,
-                                     part, bpart, s2, &r, true),
-                   "step_forward pipelined wgrad");
+        HIPCHK(marf_launch_wgrad(w, s2), l == 0 && f0 ? "step_forward pipelined wgrad_l0" : "step_forward pipelined wgrad");
     }
     return MARF_OK;
 }
@@ -1399,16 +1450,12 @@ static int step2_backward(const marf_net* net, const StepBufs& bufs, const void*
     float* bpart = (float*)(sv + p.bpart);
     const float* denom = d_loss_out + 1;
     const int nl = net->n_layers;
-    // the saved tensors' precision (fp16x2: fp16, carrying the dgrad's 2^10 gradient scale)
-    const int sdt = q.variant == 3 ? 2 : 1;
+    // (fp16x2: the saved tensors carry the dgrad's 2^10 gradient scale)
     const float post = q.variant == 3 ? 1.0f / 1024.0f : 1.0f;
-    // layer n-2 rebuilds its dz_{n-1} from these (p.dzl: the step kernel stored them instead)
-    WgDzlSrc dzl_src = {nullptr, nullptr, nullptr};
-    if (p.dzl) dzl_src = {sv + p.dzl_g, sv + p.dzl_mk, sv + p.dzl_w};
     // The fused weight gradients (marf_launch_wgrad_fused): the hidden layers in one launch, layer 0
     // beside it on the side stream, every reduction in one launch -- the same partials and sums as
     // the per-layer launches below (bit-identical).  The layer events follow it, in the per-layer order.
-    const int chunk = p.k.chunk, n_chunks = p.k.n;  // (pipeline off: the split the plan sized part / bpart by)
+    const int n_chunks = p.k.n;  // (pipeline off: the split the plan sized part / bpart by)
     if (d_dparams && !p.pipe.on && p.fused_res) {
         const int* kmap = (const int*)(sv + p.kmap);
         const bool f0 = l0_recompute(net, g, p.S);
@@ -1417,13 +1464,12 @@ static int step2_backward(const marf_net* net, const StepBufs& bufs, const void*
         int nf = 0;
         {
             const int l = nl - 1;  // the last layer: the step kernel's per-block partials
-            WgFusedLayer& x = Lf[nf++];
-            x.kind = 3;
-            x.partial = (float*)(sv + p.wlast);
-            x.bpartial = (float*)(sv + p.blast);
+            WgFusedLayer& x = Lf[nf++];  // (no product: a reduction only)
+            x.job.partial = (float*)(sv + p.wlast);
+            x.job.bpartial = (float*)(sv + p.blast);
             x.n_parts = p.nblk;
-            x.M = 3;
-            x.K = q.Kl;
+            x.job.M = 3;
+            x.job.K = q.Kl;
             x.Mo = 3;
             x.Ko = net->dims[l];
             x.dW = d_dparams + net->w_off[l];
@@ -1431,23 +1477,15 @@ static int step2_backward(const marf_net* net, const StepBufs& bufs, const void*
         }
         for (int l = nl - 2; l >= 0; --l) {
             WgFusedLayer& x = Lf[nf++];
-            x.kind = l > 0 ? 0 : (f0 ? 1 : 2);
-            x.dz = sv + p.dz[l + 1];
-            x.ldz = net->Kp[l + 1];
-            x.feat = (l == 0 && f0) ? nullptr : sv + p.feat[l];
-            x.ldf = x.K = l == 0 ? q.ldf0 : net->Kp[l];
-            x.M = net->Mp[l];
-            x.partial = (float*)(sv + p.partl[l]);
-            x.bpartial = (float*)(sv + p.bpartl[l]);
+            x.job = step2_wg_job(net, g, p, sv, l, p.k, (float*)(sv + p.partl[l]), (float*)(sv + p.bpartl[l]), f0);
             x.n_parts = n_chunks;
             x.Mo = net->dims[l + 1];
             x.Ko = net->dims[l];
             x.dW = d_dparams + net->w_off[l];
             x.db = d_dparams + net->b_off[l];
             x.kmap = l == 0 ? kmap : nullptr;
-            if (p.dzl && l == nl - 2) x.dzl = dzl_src;
         }
-        if (marf_wgrad_fused_ok(Lf, nf, p.S, chunk, n_chunks, g.Np_pad, net->L)) {
+        if (marf_wgrad_fused_ok(Lf, nf)) {
             PipeStreams* st = nullptr;
             rc = pipe_streams(&st);
             if (rc) return rc;
@@ -1461,8 +1499,7 @@ static int step2_backward(const marf_net* net, const StepBufs& bufs, const void*
                 }
                 {
                     MarfProfScope ps("wgrad_fused", s);
-                    HIPCHK(marf_launch_wgrad_fused(Lf, nf, p.S, chunk, n_chunks, g, (const float*)(sv + p.c2f),
-                                                   net->L, q.nk0w, d_gout, denom, s, st->s2, st->ev[0], st->ev[1], sdt, post),
+                    HIPCHK(marf_launch_wgrad_fused(Lf, nf, d_gout, denom, s, st->s2, st->ev[0], st->ev[1], post),
                            "step_backward fused weight gradients");
                 }
                 if (dh_side) {
@@ -1519,16 +1556,8 @@ static int step2_backward(const marf_net* net, const StepBufs& bufs, const void*
             const int K = l == 0 ? q.ldf0 : net->Kp[l];
             {
                 MarfProfScope ps(l == 0 ? "wgrad_l0" : "wgrad_hidden", s);
-                if (l == 0 && f0)
-                    HIPCHK(marf_launch_wgrad_l0_recompute(sv + p.dz[1], net->Kp[1], g, (const float*)(sv + p.c2f), net->L,
-                                                          q.nk0w, q.ldf0, p.S, net->Mp[0], chunk, n_chunks, part, bpart, s,
-                                                          nullptr, sdt),
-                           "step_backward wgrad_l0 (feat_0 recomputed)");
-                else
-                    HIPCHK(marf_launch_wgrad(sdt, sv + p.dz[l + 1], net->Kp[l + 1], sv + p.feat[l], K, p.S, net->Mp[l], K,
-                                             chunk, n_chunks, part, bpart, s, nullptr, true,
-                                             p.dzl && l == nl - 2 ? &dzl_src : nullptr),
-                           "step_backward wgrad");
+                HIPCHK(marf_launch_wgrad(step2_wg_job(net, g, p, sv, l, p.k, part, bpart, f0), s),
+                       l == 0 && f0 ? "step_backward wgrad_l0 (feat_0 recomputed)" : "step_backward wgrad");
             }
             {
                 MarfProfScope ps("wgrad_reduce", s);
@@ -1694,8 +1723,7 @@ int marf_step_backward_ev(const marf_net* net, const marf_geometry* geo, const v
         for (int l = nl - 2; l >= 0; --l) {
             {
                 MarfProfScope ps(l == 0 ? "wgrad_l0" : "wgrad_hidden", s);
-                HIPCHK(marf_launch_wgrad(net->kdt, sv + p.dz[l + 1], net->Kp[l + 1], sv + p.feat[l], net->Kp[l], S,
-                                         net->Mp[l], net->Kp[l], p.k.chunk, p.k.n, part, bpart, s),
+                HIPCHK(marf_launch_wgrad(wg_job(wg_shape(*net, l, S, p.k), sv + p.dz[l + 1], sv + p.feat[l], part, bpart), s),
                        "step_backward wgrad");
             }
             {
@@ -1966,18 +1994,13 @@ int marf_mask_backward(const marf_mask_net* net, const marf_geometry* geo, const
     for (int l = 0; l < nl - 1; ++l) {
         {
             MarfProfScope ps(l == 0 ? "mask_wgrad_l0" : "mask_wgrad_hidden", s);
+            WgJob w = wg_job(wg_shape(*net, l, S, wp.k), ws + wp.dz[l + 1], sv + sp.feat[l], part, bpart);
             if (net->split) {  // hi plane [S][Kp], the lo plane behind it
-                const char* dzp = ws + wp.dz[l + 1];
-                const char* ftp = sv + sp.feat[l];
-                HIPCHK(marf_launch_wgrad_split(dzp, dzp + (size_t)S * net->Kp[l + 1] * 2, net->Kp[l + 1], ftp,
-                                               ftp + (size_t)S * net->Kp[l] * 2, net->Kp[l], S, net->Mp[l], net->Kp[l],
-                                               wp.k.chunk, wp.k.n, part, bpart, s),
-                       "mask_backward wgrad");
-            } else {
-                HIPCHK(marf_launch_wgrad(net->kdt, ws + wp.dz[l + 1], net->Kp[l + 1], sv + sp.feat[l], net->Kp[l], S,
-                                         net->Mp[l], net->Kp[l], wp.k.chunk, wp.k.n, part, bpart, s),
-                       "mask_backward wgrad");
+                w.split = true;
+                w.dz_lo = (const char*)w.dz + (size_t)S * net->Kp[l + 1] * 2;
+                w.feat_lo = (const char*)w.feat + (size_t)S * net->Kp[l] * 2;
             }
+            HIPCHK(marf_launch_wgrad(w, s), "mask_backward wgrad");
         }
         MarfProfScope ps("mask_wgrad_reduce", s);
         HIPCHK(marf_launch_wgrad_reduce(part, bpart, wp.k.n, net->Mp[l], net->Kp[l], net->dims[l + 1],

@@ -185,13 +185,18 @@ hipError_t marf_launch_reduce_dH(const float* partial, int tiles_per_patch, int 
                                  const float* denom = nullptr);
 hipError_t marf_launch_mlp_fwd(const marf::FwdArgs& a, int dtype, int TP, size_t lds, int n_tiles, hipStream_t s);
 hipError_t marf_launch_mlp_bwd(const marf::BwdArgs& a, int dtype, int TP, size_t lds, int n_tiles, hipStream_t s);
+// ---- weight gradients (marf_wgrad.hip): dW_l = sum_px dz_{l+1} (x) feat_l as split-K partials
+// [n_chunks][M][K] (+ [n_chunks][M] for the bias), then a fixed-order reduction.  A gradient is
+// described once, as a WgJob: its shape (all that decides the kernel, known when the buffers are
+// planned) and its pointers.  wg_pick holds every kernel's shape conditions: the plans ask it what
+// a launch will do, marf_launch_wgrad does what it says.
+
 // one piece of a pipelined step's weight gradients: n blocks split the pixel rows [s_lo, s_lo + s_len)
 // and write split-K partials part0 .. part0 + n - 1
 struct WgRange {
     long long s_lo, s_len;
     int n, part0;
 };
-bool marf_wgrad_range_ok(int dtype, int M, int ldz, int K, int ldf);
 // dz_{n-1} recomputed by the weight gradient of layer n-2 instead of read: what the step kernel
 // stored in its place (DZL_G_SET .. above: per-set g fragments and mask words, the dgrad stage's weights)
 struct WgDzlSrc {
@@ -199,49 +204,149 @@ struct WgDzlSrc {
     const char* mk;
     const char* w;
 };
-// the shape the recomputing instantiation takes: a 256 x 256 bf16 T16 layer on the LDS-DMA kernel
-bool marf_wgrad_dzl_ok(int M, int ldz, int K, int ldf, long long S, int chunk, int n_chunks);
-// (L: the net's posenc bands; feat_0 is recomputed for L <= 16 only)
-bool marf_wgrad_l0_recompute_ok(int M, int ldz, int ldf0, int L, long long S, int chunk, int n_chunks,
-                                long long Np_pad);
-hipError_t marf_launch_wgrad_l0_recompute(const void* dz, int ldz, const GeoDev& geo, const float* c2f_w, int L,
-                                          int nk0, int K0, long long S, int M, int chunk, int n_chunks, float* partial,
-                                          float* bpartial, hipStream_t s, const WgRange* rng = nullptr, int dtype = 1);
-// t16: dz / feat in the split-recipe step kernel's T16 block layout (marf_wgrad.hip t16_off)
-hipError_t marf_launch_wgrad(int dtype, const void* dz, int ldz, const void* feat, int ldf, long long S, int M, int K,
-                             int chunk, int n_chunks, float* partial, float* bpartial, hipStream_t s,
-                             const WgRange* rng = nullptr, bool t16 = false, const WgDzlSrc* dzl = nullptr);
-// One layer of the fused weight-gradient launch (marf_launch_wgrad_fused): its split-K partials
-// [n_parts][M][K] (+ [n_parts][M] bias) and the fixed-order reduction into dW [Mo][Ko] / db [Mo].
+struct WgShape {
+    int dtype;            // 0 fp32, 1 bf16, 2 fp16
+    int M, ldz, K, ldf;   // output rows (<= ldz) and columns (<= ldf); the operands' row strides
+    long long S;          // pixel rows
+    int chunk, n_chunks;  // the split-K rule (range mode: chunk unused, n_chunks = the range's blocks)
+    bool t16;             // dz / feat in the split-recipe step kernel's T16 block layout (marf_wgrad.hip t16_off)
+    bool split;           // MARF_BF16X3A (the mask net): each operand as bf16 hi + lo planes,
+                          // dW = dz_h^T a_h + dz_h^T a_l + dz_l^T a_h, db = sum (dz_h + dz_l)
+    bool f0;              // layer 0 with feat_0 recomputed on chip, not read (K = ldf: the step kernel's ldf0)
+    bool dzl;             // layer n-2 with dz_{n-1} recomputed, not read (WgDzlSrc)
+    bool ranged;          // range mode (WgRange)
+    int L;                // f0: the net's posenc bands
+    long long Np_pad;     // f0: pixel slots per patch
+};
+struct WgJob : WgShape {
+    const void* dz;       // [S][ldz] (split: the hi plane)
+    const void* dz_lo;    // split only
+    const void* feat;     // [S][ldf] (split: the hi plane; f0: unused)
+    const void* feat_lo;  // split only
+    float* partial;       // [n_chunks][M][K]
+    float* bpartial;      // [n_chunks][M], may be null
+    WgDzlSrc dzl_src;     // dzl
+    const GeoDev* f0_geo; // f0: the step's crop grid, its band weights (null: c2f off) and feat_0's
+    const float* c2f_w;   //     column layout (k_step2's layer-0 k-steps)
+    int nk0;
+    WgRange rng;          // ranged
+};
+enum WgKernel { WG_NONE, WG_STAGED, WG_STAGED_SPLIT, WG_DMA256, WG_DMA96, WG_DMA_F0, WG_DMA_DZL };
+struct WgPick {
+    WgKernel k;
+    int bm, bn;  // its output block (WG_STAGED: 256 x 256, 256 x 128, 256 x 64 or 128 x 64)
+    constexpr int blocks(const WgShape& w) const { return ((w.M + bm - 1) / bm) * ((w.K + bn - 1) / bn); }
+};
+constexpr int WG_SPH = 32, WG_SP0 = 64;  // LDS-DMA stage heights: hidden layers, recomputed layer 0
+constexpr int F0_PATCHES = 4;            // patches a recomputed layer-0 chunk may span
+constexpr int WG_RANGE_CHUNK = 64;       // range mode's chunk: a multiple of every stage height it splits at
+
+// The kernel an M x K weight gradient runs on, WG_NONE if there is none (a launch of it is an error).
+constexpr WgPick wg_pick(const WgShape& w, bool dma_enabled) {
+    constexpr WgPick none = {WG_NONE, 0, 0};
+    const int chunk = w.ranged ? WG_RANGE_CHUNK : w.chunk;
+    if (w.split)  // register-staged, 32-pixel stages; the mask net's layer 0 (K = 448) takes two column blocks
+        return w.dtype == 1 && !w.t16 && !w.f0 && !w.dzl && !w.ranged && w.ldz % 8 == 0 && w.ldf % 8 == 0 &&
+                       chunk % 32 == 0 && w.n_chunks >= 1
+                   ? WgPick{WG_STAGED_SPLIT, 256, 256}
+                   : none;
+    // feat_0 recomputed: 256-wide layer 0, the 64-wide feat_0 of L <= 12 or the 96-wide one of
+    // L = 13..16 (both built in the 96-wide stage; a 64-wide partial takes its first 64 columns).
+    // L <= 16: the stage's 16 threads per row build two bands of one coordinate each, so bands
+    // 16..19 of L = 17..20 (feat_0 96 wide too) would stay unwritten; those nets store and read feat_0
+    if (w.f0)
+        return w.dtype != 0 && !w.dzl && w.M == 256 && w.ldz % 8 == 0 && w.ldz >= w.M && (w.ldf == 96 || w.ldf == 64) &&
+                       w.K == w.ldf && w.L <= 16 && w.S % WG_SP0 == 0 && chunk % WG_SP0 == 0 && w.Np_pad > 0 &&
+                       w.Np_pad < (1 << 24) && (chunk + w.Np_pad - 1) / w.Np_pad + 1 <= F0_PATCHES
+                   ? WgPick{WG_DMA_F0, 256, 96}
+                   : none;
+    // LDS-DMA ring: 256-wide dz blocks with a 256-wide (hidden) or 96-wide (layer 0, L = 16) feat
+    const bool dma = w.dtype != 0 && w.M % 256 == 0 && w.ldz % 8 == 0 && w.ldz >= w.M && w.S % WG_SPH == 0 &&
+                     chunk % WG_SPH == 0 && (long long)w.n_chunks * (w.M / 256) * ((w.K + 255) / 256) <= 0x7fffffff &&
+                     dma_enabled;
+    const bool dma256 = dma && w.K % 256 == 0 && w.ldf % 8 == 0 && w.ldf >= w.K, dma96 = dma && w.K == 96 && w.ldf == 96;
+    if (w.dzl)  // one 256 x 256 block of bf16 T16 tensors
+        return dma256 && w.dtype == 1 && w.t16 && !w.ranged && w.M == 256 && w.K == 256 && w.ldz == 256 && w.n_chunks >= 1
+                   ? WgPick{WG_DMA_DZL, 256, 256}
+                   : none;
+    if (w.ranged && !(dma256 || dma96)) return none;  // range mode: the LDS-DMA kernel only
+    if (w.t16 && w.dtype == 0) return none;           // T16: 16-bit tensors of the step kernel only
+    if (dma256) return {WG_DMA256, 256, 256};
+    if (dma96) return {WG_DMA96, 256, 96};
+    if (w.M >= 256 && w.K >= 192) return {WG_STAGED, 256, 256};
+    if (w.M >= 256 && w.K > 64) return {WG_STAGED, 256, 128};  // layer 0 at L = 16 reads dz once
+    return {WG_STAGED, w.M >= 256 ? 256 : 128, 64};
+}
+// what the kernels did before their conditions were gathered here (each row read off that code)
+namespace wg_pinned {
+// the C3 hidden layer, row-major: bf16, 256 x 256, S and chunk multiples of 32
+constexpr WgShape hidden() {
+    WgShape w = {};
+    w.dtype = 1;
+    w.M = w.ldz = w.K = w.ldf = 256;
+    w.S = 4 * 65536;
+    w.chunk = 1024;
+    w.n_chunks = 256;
+    return w;
+}
+constexpr WgShape prec(WgShape w, int dtype) { return w.dtype = dtype, w; }
+constexpr WgShape rows(WgShape w, int M) { return w.M = w.ldz = M, w; }
+constexpr WgShape cols(WgShape w, int K) { return w.K = w.ldf = K, w; }
+constexpr WgShape stride(WgShape w, int ldf) { return w.ldf = ldf, w; }
+constexpr WgShape t16(WgShape w) { return w.t16 = true, w; }
+constexpr WgShape planes(WgShape w) { return w.split = true, w; }
+constexpr WgShape dzl(WgShape w) { return w.dzl = true, w; }
+constexpr WgShape ranged(WgShape w) { return w.ranged = true, w.chunk = 0, w.n_chunks = 28, w; }
+constexpr WgShape f0(WgShape w, int L) { return w.f0 = true, w.L = L, w.Np_pad = 65536, cols(w, 96); }
+constexpr bool is(const WgShape& w, bool dma, WgKernel k, int bm = 0, int bn = 0) {
+    const WgPick p = wg_pick(w, dma);
+    return p.k == k && (k != WG_STAGED || (p.bm == bm && p.bn == bn));
+}
+constexpr WgShape c3 = t16(hidden());  // ... as the step kernel saves it
+static_assert(is(c3, true, WG_DMA256), "C3 hidden layer");
+static_assert(is(dzl(c3), true, WG_DMA_DZL), "... with dz recomputed");
+static_assert(is(prec(c3, 0), true, WG_NONE), "T16 with fp32");
+static_assert(is(prec(hidden(), 0), true, WG_STAGED, 256, 256), "C3 hidden layer's shape in fp32");
+static_assert(is(c3, false, WG_STAGED, 256, 256), "... with MARF_WGRAD_DMA=0");
+static_assert(is(cols(c3, 96), true, WG_DMA96), "K = ldf = 96, bf16");
+static_assert(is(cols(c3, 96), false, WG_STAGED, 256, 128), "... with MARF_WGRAD_DMA=0");
+static_assert(is(f0(c3, 16), true, WG_DMA_F0) && is(f0(c3, 16), false, WG_DMA_F0), "feat_0 recomputed at L = 16");
+static_assert(is(f0(c3, 17), true, WG_NONE), "feat_0 recomputed at L = 17");
+static_assert(is(rows(hidden(), 128), true, WG_STAGED, 128, 64), "M = 128");
+static_assert(is(cols(rows(hidden(), 512), 512), true, WG_DMA256), "M = 512, K = 512, bf16");
+static_assert(is(prec(ranged(c3), 0), true, WG_NONE), "range mode with fp32");
+static_assert(is(cols(ranged(c3), 64), true, WG_NONE), "range mode with K = 64");
+static_assert(is(ranged(c3), true, WG_DMA256) && is(ranged(c3), false, WG_NONE), "range mode: the LDS-DMA kernel only");
+static_assert(is(planes(cols(hidden(), 448)), true, WG_STAGED_SPLIT) && is(planes(cols(hidden(), 448)), false, WG_STAGED_SPLIT),
+              "hi + lo planes with K = 448");
+static_assert(is(dzl(c3), false, WG_NONE), "dz recomputed: the LDS-DMA kernel only");
+static_assert(is(ranged(dzl(c3)), true, WG_NONE), "dz recomputed in range mode");
+static_assert(is(prec(c3, 2), true, WG_DMA256) && is(dzl(prec(c3, 2)), true, WG_NONE), "fp16x2");
+static_assert(is(cols(hidden(), 64), true, WG_STAGED, 256, 64), "layer 0 at L <= 12, stored");
+static_assert(is(stride(hidden(), 260), true, WG_STAGED, 256, 256), "a feat stride the DMA cannot take");
+}  // namespace wg_pinned
+
+// MARF_WGRAD_DMA (A/B switch, read here at every call: 0 = register-staged kernels) into wg_pick
+WgPick marf_wgrad_pick(const WgShape& w);
+hipError_t marf_launch_wgrad(const WgJob& j, hipStream_t s);
+// One layer of the fused weight-gradient launch (marf_launch_wgrad_fused): its product (job.dz null:
+// none, the partials are there already) and the fixed-order reduction of n_parts partials into dW
+// [Mo][Ko] / db [Mo]
 struct WgFusedLayer {
-    int kind;                 // 0: 256 x 256 LDS-DMA (hidden layer); 1: layer 0, feat_0 recomputed (256 x 96);
-                              // 2: layer 0 stored (marf_launch_wgrad's kernel); 3: reduction only
-    const void* dz;           // kinds 0..2: [S][ldz] bf16 (fp16x2: fp16)
-    const void* feat;         // kinds 0, 2: [S][ldf] bf16 (fp16x2: fp16)
-    int ldz, ldf, M, K;
-    float* partial;
-    float* bpartial;
-    int n_parts;              // partials to reduce (kinds 0..2: the launch's n_chunks)
+    WgJob job;
+    int n_parts;      // partials to reduce (with a product: its n_chunks)
     int Mo, Ko;
     float* dW;
     float* db;
-    const int* kmap;          // layer 0: column of true input feature k in the partial
-    WgDzlSrc dzl;             // kind 0, g != null: dz is recomputed, not read (layer n-2)
+    const int* kmap;  // layer 0: column of true input feature k in the partial
 };
-// every kind-0 layer's chunk products in one launch on s, the layer-0 one (kind 1 or 2) beside it on
-// s2 (fork / join events), then every layer's reduction in one launch on s; false if a shape does
-// not qualify
-bool marf_wgrad_fused_ok(const WgFusedLayer* layers, int n_layers, long long S, int chunk, int n_chunks,
-                         long long Np_pad, int L_bands);
-hipError_t marf_launch_wgrad_fused(const WgFusedLayer* layers, int n_layers, long long S, int chunk, int n_chunks,
-                                   const GeoDev& f0_geo, const float* c2f_w, int L, int nk0, const float* gscale,
-                                   const float* denom, hipStream_t s, hipStream_t s2, hipEvent_t fork, hipEvent_t join,
-                                   int dtype = 1, float post = 1.f);  // dtype 2 / post 2^-10: the fp16x2 recipe
-// MARF_BF16X3A (the mask net): dW = dz_h^T a_h + dz_h^T a_l + dz_l^T a_h, db = sum (dz_h + dz_l), each
-// operand given as its hi and lo [S][ld] bf16 planes; the same [n_chunks][M][K] partials as marf_launch_wgrad
-hipError_t marf_launch_wgrad_split(const void* dz_hi, const void* dz_lo, int ldz, const void* feat_hi,
-                                   const void* feat_lo, int ldf, long long S, int M, int K, int chunk, int n_chunks,
-                                   float* partial, float* bpartial, hipStream_t s);
+// every layer on a one-block LDS-DMA 256 kernel (the hidden layers) in one launch on s, the one
+// other product (layer 0) beside it on s2 (fork / join events), then every layer's reduction in one
+// launch on s; false if a shape does not qualify.  post: the exact power of two the products'
+// partials carry the inverse of (2^-10: the fp16x2 recipe)
+bool marf_wgrad_fused_ok(const WgFusedLayer* layers, int n_layers);
+hipError_t marf_launch_wgrad_fused(const WgFusedLayer* layers, int n_layers, const float* gscale, const float* denom,
+                                   hipStream_t s, hipStream_t s2, hipEvent_t fork, hipEvent_t join, float post = 1.f);
 hipError_t marf_launch_wgrad_last(int dtype, const float* glast, const void* feat, long long S, int ldf, int K,
                                   int chunk, int n_chunks, float* partial, float* bpartial, hipStream_t s);
 hipError_t marf_launch_wgrad_reduce(const float* partial, const float* bpartial, int n_chunks, int M, int K, int Mo,

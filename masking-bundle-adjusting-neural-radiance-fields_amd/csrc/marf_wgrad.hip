@@ -51,14 +51,8 @@ struct WgArgs {
     int rng_n, part0;
     int t16;           // dz / feat in the step kernel's T16 block layout (t16_off), not row-major
     WgDzlSrc dzl;      // g != null (k_wgrad_dma's DZL instantiations): dz is not read but recomputed
-    const void* dz_lo;    // k_wgrad_split: the lo planes of dz and feat (dz / feat: the hi planes)
+    const void* dz_lo;    // two planes per operand: the lo planes of dz and feat (dz / feat: the hi planes)
     const void* feat_lo;
-};
-
-template <int RT, int CT>
-struct WgGeo {
-    static constexpr int BM = 4 * RT * 32;
-    static constexpr int BN = 2 * CT * 32;
 };
 
 MARF_DEV i16x4 tr_read(const void* p) {  // (an address for the instruction: no typed access)
@@ -82,27 +76,90 @@ MARF_DEV int t16_lds(int r, int c, int nb) {  // byte offset of (stage row r, fe
     return ((r >> 5) * nb + b) * 1024 + (r & 31) * 32 + (c & 15) * 2;
 }
 
-// the product of pixel chunk `chunk_id` into output block `ob` (the body of one k_wgrad block;
-// also a work item of k_wgrad_fused)
-template <class P, int RT, int CT, int SP>
+// ---- the register-staged kernel: any shape, any arithmetic; one stage in flight behind the MFMAs
+// A stage is SP pixel rows of the block's dz and feat columns, NPL planes each (one, or bf16 hi + lo):
+// global memory -> registers (16-byte vectors, zero outside the chunk / the matrix) -> LDS tiles
+// [NPL][SP][LD] per operand (rows padded: the head of this file).
+template <class T>
+constexpr int WG_PADE = sizeof(T) == 2 ? 32 : 4;  // row padding (elements), keeps rows 16-B aligned
+
+template <class T, int RT, int CT, int SP, int NPL>
+constexpr size_t wg_staged_lds() {  // both operands' tiles; at least the bias fold's 512 floats
+    const size_t t = (size_t)NPL * SP * (4 * RT * 32 + 2 * CT * 32 + 2 * WG_PADE<T>) * sizeof(T);
+    return t < 512 * sizeof(float) ? 512 * sizeof(float) : t;
+}
+
+// The product of pixel chunk `chunk_id` into output block `ob` (the body of one k_wgrad block).
+// NPL = 2 (MARF_BF16X3A, the mask net): both operands split into bf16 hi + lo planes, each read from
+// HBM once into tiles of its own; per 16-pixel k-step every accumulator tile takes 3 MFMAs,
+//   dW = dz_h^T a_h + dz_h^T a_l + dz_l^T a_h,   db = sum (dz_h + dz_l)   (fp32)
+// into the same [chunks][M][K] partials, so the fixed-order reduction is shared.
+template <class P, int RT, int CT, int SP, int NPL>
 MARF_DEV void wgrad_body(const WgArgs& a, int chunk_id, int ob, char* smem) {
     typedef typename P::T T;
-    constexpr int BM = WgGeo<RT, CT>::BM, BN = WgGeo<RT, CT>::BN;
-    constexpr int PADE = sizeof(T) == 2 ? 32 : 4;  // row padding (elements), keeps rows 16-B aligned
-    constexpr int LDZ = BM + PADE, LDF = BN + PADE;
-    constexpr int VEC = 16 / sizeof(T);          // elements per 16-byte vector
-    constexpr int NVZ = SP * BM / VEC / 512;     // dz vectors per thread and stage
-    constexpr int NVF = SP * BN / VEC / 512;     // feat vectors per thread and stage
-    T* tz = reinterpret_cast<T*>(smem);          // [SP][LDZ]
-    T* tf = tz + SP * LDZ;                        // [SP][LDF]
+    static_assert(NPL == 1 || (NPL == 2 && std::is_same<P, PrecBF16>::value), "planes per operand");
+    constexpr int BM = 4 * RT * 32, BN = 2 * CT * 32;
+    constexpr int LDZ = BM + WG_PADE<T>, LDF = BN + WG_PADE<T>;
+    constexpr int VEC = 16 / sizeof(T);       // elements per 16-byte vector
+    constexpr int NVZ = SP * BM / VEC / 512;  // dz vectors per thread, stage and plane
+    constexpr int NVF = SP * BN / VEC / 512;  // feat vectors per thread, stage and plane
+    static_assert(NVZ >= 1 && NVF >= 1 && SP % 16 == 0, "stage shape");
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wr = wave >> 1, wc = wave & 1;
     const int m0 = (ob / a.n_oblk_c) * BM, k0 = (ob % a.n_oblk_c) * BN;
     const long long s_begin = (long long)chunk_id * a.chunk;
     const long long s_end = min(s_begin + a.chunk, a.S);
     const bool do_bias = a.bpartial && (ob % a.n_oblk_c) == 0;
-    const T* dz = reinterpret_cast<const T*>(a.dz);
-    const T* ft = reinterpret_cast<const T*>(a.feat);
+    T* tz = reinterpret_cast<T*>(smem);  // [NPL][SP][LDZ]
+    T* tf = tz + NPL * SP * LDZ;         // [NPL][SP][LDF]
+    const T* zs[2] = {reinterpret_cast<const T*>(a.dz), reinterpret_cast<const T*>(a.dz_lo)};
+    const T* fs[2] = {reinterpret_cast<const T*>(a.feat), reinterpret_cast<const T*>(a.feat_lo)};
+
+    // The dz loop and the feat loop of a stage are written out twice, on purpose: every form that
+    // wrote them once (an operand struct, a generic lambda, a function template, one loop over both
+    // operands' vectors) moved the register allocation of most instantiations by 2 to 6 VGPRs and
+    // made the fp32 kernels 2 % slower (profiles/wgrad_refactor/README.md)
+    uint4 rz[NVZ][NPL], rf[NVF][NPL];
+    auto load_stage = [&](long long s0) {
+#pragma unroll
+        for (int q = 0; q < NVZ; ++q) {
+            const int e = threadIdx.x + 512 * q;
+            const int r = e / (BM / VEC), c = (e % (BM / VEC)) * VEC;
+#pragma unroll
+            for (int p = 0; p < NPL; ++p) rz[q][p] = make_uint4(0, 0, 0, 0);
+            if (s0 + r < s_end && m0 + c < a.M) {
+                const size_t o = a.t16 ? t16_off(s0 + r, m0 + c, a.ldz) : (size_t)((s0 + r) * a.ldz + m0 + c);
+#pragma unroll
+                for (int p = 0; p < NPL; ++p) rz[q][p] = ld_as<uint4>(zs[p] + o);
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < NVF; ++q) {
+            const int e = threadIdx.x + 512 * q;
+            const int r = e / (BN / VEC), c = (e % (BN / VEC)) * VEC;
+#pragma unroll
+            for (int p = 0; p < NPL; ++p) rf[q][p] = make_uint4(0, 0, 0, 0);
+            if (s0 + r < s_end && k0 + c < a.K) {
+                const size_t o = a.t16 ? t16_off(s0 + r, k0 + c, a.ldf) : (size_t)((s0 + r) * a.ldf + k0 + c);
+#pragma unroll
+                for (int p = 0; p < NPL; ++p) rf[q][p] = ld_as<uint4>(fs[p] + o);
+            }
+        }
+    };
+    auto store_stage = [&]() {
+#pragma unroll
+        for (int q = 0; q < NVZ; ++q) {
+            const int e = threadIdx.x + 512 * q;
+            const int r = e / (BM / VEC), c = (e % (BM / VEC)) * VEC;
+            for (int p = 0; p < NPL; ++p) st_as<uint4>(tz + (p * SP + r) * LDZ + c, rz[q][p]);
+        }
+#pragma unroll
+        for (int q = 0; q < NVF; ++q) {
+            const int e = threadIdx.x + 512 * q;
+            const int r = e / (BN / VEC), c = (e % (BN / VEC)) * VEC;
+            for (int p = 0; p < NPL; ++p) st_as<uint4>(tf + (p * SP + r) * LDF + c, rf[q][p]);
+        }
+    };
 
     f32x16 acc[RT][CT];
 #pragma unroll
@@ -111,41 +168,18 @@ MARF_DEV void wgrad_body(const WgArgs& a, int chunk_id, int ob, char* smem) {
         for (int j = 0; j < CT; ++j) acc[i][j] = (f32x16){};
     float bsum = 0.f;
 
-    // stage s0 -> registers (16-byte vectors, zero outside the chunk / the matrix)
-    uint4 rz[NVZ], rf[NVF];
-    auto load_stage = [&](long long s0) {
-#pragma unroll
-        for (int q = 0; q < NVZ; ++q) {
-            const int e = threadIdx.x + 512 * q;
-            const int r = e / (BM / VEC), c = (e % (BM / VEC)) * VEC;
-            rz[q] = make_uint4(0, 0, 0, 0);
-            if (s0 + r < s_end && m0 + c < a.M)
-                rz[q] = ld_as<uint4>(dz + (a.t16 ? t16_off(s0 + r, m0 + c, a.ldz) : (size_t)((s0 + r) * a.ldz + m0 + c)));
-        }
-#pragma unroll
-        for (int q = 0; q < NVF; ++q) {
-            const int e = threadIdx.x + 512 * q;
-            const int r = e / (BN / VEC), c = (e % (BN / VEC)) * VEC;
-            rf[q] = make_uint4(0, 0, 0, 0);
-            if (s0 + r < s_end && k0 + c < a.K)
-                rf[q] = ld_as<uint4>(ft + (a.t16 ? t16_off(s0 + r, k0 + c, a.ldf) : (size_t)((s0 + r) * a.ldf + k0 + c)));
+    // the MFMA operand of k-step ks from the 32 columns at c0 of a tile: 16-bit, a transposed read
+    // (this lane supplies rows r0 and r0 + 4); fp32, one element per lane straight from the tile
+    auto frag = [&](const T* tile, int ld, int ks, int c0) -> typename P::frag {
+        if constexpr (sizeof(T) == 2) {
+            const int g = lane >> 4, gi = lane & 15;
+            const T* base = tile + (ks + 8 * (g >> 1) + (gi >> 2)) * ld + c0 + 16 * (g & 1) + 4 * (gi & 3);
+            return frag_of<typename P::frag>(tr_read(base), tr_read(base + 4 * ld));
+        } else {
+            return tile[(ks + (lane >> 5)) * ld + c0 + (lane & 31)];
         }
     };
-    auto store_stage = [&]() {
-#pragma unroll
-        for (int q = 0; q < NVZ; ++q) {
-            const int e = threadIdx.x + 512 * q;
-            const int r = e / (BM / VEC), c = (e % (BM / VEC)) * VEC;
-            st_as<uint4>(tz + r * LDZ + c, rz[q]);
-        }
-#pragma unroll
-        for (int q = 0; q < NVF; ++q) {
-            const int e = threadIdx.x + 512 * q;
-            const int r = e / (BN / VEC), c = (e % (BN / VEC)) * VEC;
-            st_as<uint4>(tf + r * LDF + c, rf[q]);
-        }
-    };
-
+    constexpr int RSTEP = 512 / BM > 0 ? 512 / BM : 1;  // bias: rows summed side by side
     if (s_begin < s_end) load_stage(s_begin);
     for (long long s0 = s_begin; s0 < s_end; s0 += SP) {
         __syncthreads();  // previous stage fully consumed
@@ -155,47 +189,38 @@ MARF_DEV void wgrad_body(const WgArgs& a, int chunk_id, int ob, char* smem) {
 
         if (do_bias) {
             // db partial: thread t sums column t%BM over rows t/BM, t/BM + 512/BM, ...
-            constexpr int RSTEP = 512 / BM > 0 ? 512 / BM : 1;
             const int c = threadIdx.x % BM, r0 = threadIdx.x / BM;
             if (r0 < RSTEP)
-                for (int r = r0; r < SP; r += RSTEP) bsum += P::tof(tz[r * LDZ + c]);
+                for (int r = r0; r < SP; r += RSTEP) {
+                    if constexpr (NPL == 1) bsum += P::tof(tz[r * LDZ + c]);
+                    else bsum += bf2f(tz[r * LDZ + c]) + bf2f(tz[(SP + r) * LDZ + c]);
+                }
         }
-
-        if constexpr (sizeof(T) == 2) {
-            const int g = lane >> 4, gi = lane & 15, q = gi >> 2, p4 = gi & 3;
+        // one k-step (16 pixels of 16-bit operands, 2 of fp32): every accumulator tile takes hi x hi;
+        // then, over the tiles again, hi x lo and lo x hi
 #pragma unroll
-            for (int ks = 0; ks < SP; ks += 16) {
-                const int r0 = ks + 8 * (g >> 1) + q;  // this lane supplies row r0 (and r0 + 4)
-                typename P::frag af[RT], bf[CT];
+        for (int ks = 0; ks < SP; ks += sizeof(T) == 2 ? 16 : 2) {
+            typename P::frag zf[NPL][RT], ff[NPL][CT];
 #pragma unroll
-                for (int i = 0; i < RT; ++i) {
-                    const int c0 = (wr * RT + i) * 32 + 16 * (g & 1) + 4 * p4;
-                    const u16* base = tz + r0 * LDZ + c0;
-                    af[i] = frag_of<typename P::frag>(tr_read(base), tr_read(base + 4 * LDZ));
-                }
+            for (int p = 0; p < NPL; ++p) {
 #pragma unroll
-                for (int j = 0; j < CT; ++j) {
-                    const int c0 = (wc * CT + j) * 32 + 16 * (g & 1) + 4 * p4;
-                    const u16* base = tf + r0 * LDF + c0;
-                    bf[j] = frag_of<typename P::frag>(tr_read(base), tr_read(base + 4 * LDF));
-                }
+                for (int i = 0; i < RT; ++i) zf[p][i] = frag(tz + p * SP * LDZ, LDZ, ks, (wr * RT + i) * 32);
 #pragma unroll
-                for (int i = 0; i < RT; ++i)
-#pragma unroll
-                    for (int j = 0; j < CT; ++j) acc[i][j] = P::mma32(af[i], bf[j], acc[i][j]);
+                for (int j = 0; j < CT; ++j) ff[p][j] = frag(tf + p * SP * LDF, LDF, ks, (wc * CT + j) * 32);
             }
-        } else {
-            const int h = lane >> 5, rl = lane & 31;
-            for (int ks = 0; ks < SP; ks += 2) {
-                typename P::frag af[RT], bf[CT];
 #pragma unroll
-                for (int i = 0; i < RT; ++i) af[i] = tz[(ks + h) * LDZ + (wr * RT + i) * 32 + rl];
+            for (int i = 0; i < RT; ++i)
 #pragma unroll
-                for (int j = 0; j < CT; ++j) bf[j] = tf[(ks + h) * LDF + (wc * CT + j) * 32 + rl];
+                for (int j = 0; j < CT; ++j) acc[i][j] = P::mma32(zf[0][i], ff[0][j], acc[i][j]);
+            if constexpr (NPL == 2) {
 #pragma unroll
                 for (int i = 0; i < RT; ++i)
 #pragma unroll
-                    for (int j = 0; j < CT; ++j) acc[i][j] = P::mma32(af[i], bf[j], acc[i][j]);
+                    for (int j = 0; j < CT; ++j) acc[i][j] = P::mma32(zf[0][i], ff[1][j], acc[i][j]);
+#pragma unroll
+                for (int i = 0; i < RT; ++i)
+#pragma unroll
+                    for (int j = 0; j < CT; ++j) acc[i][j] = P::mma32(zf[1][i], ff[0][j], acc[i][j]);
             }
         }
     }
@@ -218,7 +243,6 @@ MARF_DEV void wgrad_body(const WgArgs& a, int chunk_id, int ob, char* smem) {
         float* bs = reinterpret_cast<float*>(smem);
         bs[threadIdx.x] = bsum;
         __syncthreads();
-        constexpr int RSTEP = 512 / BM > 0 ? 512 / BM : 1;
         if ((int)threadIdx.x < BM && m0 + (int)threadIdx.x < a.M) {
             float s = 0.f;
             for (int r = 0; r < RSTEP; ++r) s += bs[threadIdx.x + r * BM];
@@ -227,164 +251,10 @@ MARF_DEV void wgrad_body(const WgArgs& a, int chunk_id, int ob, char* smem) {
     }
 }
 
-template <class P, int RT, int CT, int SP>
+template <class P, int RT, int CT, int SP, int NPL>
 __global__ __launch_bounds__(512, 1) void k_wgrad(WgArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    wgrad_body<P, RT, CT, SP>(a, blockIdx.x, blockIdx.y, smem);
-}
-
-// ---- MARF_BF16X3A (the mask net): both operands split into bf16 hi + lo planes,
-//   dW = dz_h^T a_h + dz_h^T a_l + dz_l^T a_h,   db = sum (dz_h + dz_l)   (fp32)
-// The register-staged body above with four LDS tiles per stage (dz hi / lo, feat hi / lo), each read
-// from HBM once; per 16-pixel k-step every accumulator tile takes 3 MFMAs from transposed-read
-// fragments.  Same [chunks][M][K] partials, so the fixed-order reduction is shared.
-template <int RT, int CT, int SP>
-MARF_DEV void wgrad_split_body(const WgArgs& a, int chunk_id, int ob, char* smem) {
-    typedef PrecBF16 P;
-    typedef u16 T;
-    constexpr int BM = WgGeo<RT, CT>::BM, BN = WgGeo<RT, CT>::BN;
-    constexpr int PADE = 32;
-    constexpr int LDZ = BM + PADE, LDF = BN + PADE;
-    constexpr int VEC = 8;
-    constexpr int NVZ = SP * BM / VEC / 512;  // vectors per thread, stage and plane
-    constexpr int NVF = SP * BN / VEC / 512;
-    static_assert(NVZ >= 1 && NVF >= 1 && SP % 16 == 0, "stage shape");
-    T* tzh = reinterpret_cast<T*>(smem);  // [SP][LDZ]
-    T* tzl = tzh + SP * LDZ;
-    T* tfh = tzl + SP * LDZ;              // [SP][LDF]
-    T* tfl = tfh + SP * LDF;
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int wr = wave >> 1, wc = wave & 1;
-    const int m0 = (ob / a.n_oblk_c) * BM, k0 = (ob % a.n_oblk_c) * BN;
-    const long long s_begin = (long long)chunk_id * a.chunk;
-    const long long s_end = min(s_begin + a.chunk, a.S);
-    const bool do_bias = a.bpartial && (ob % a.n_oblk_c) == 0;
-    const T* dzh = reinterpret_cast<const T*>(a.dz);
-    const T* dzl = reinterpret_cast<const T*>(a.dz_lo);
-    const T* fth = reinterpret_cast<const T*>(a.feat);
-    const T* ftl = reinterpret_cast<const T*>(a.feat_lo);
-
-    f32x16 acc[RT][CT];
-#pragma unroll
-    for (int i = 0; i < RT; ++i)
-#pragma unroll
-        for (int j = 0; j < CT; ++j) acc[i][j] = (f32x16){};
-    float bsum = 0.f;
-
-    uint4 rzh[NVZ], rzl[NVZ], rfh[NVF], rfl[NVF];
-    auto load_stage = [&](long long s0) {
-#pragma unroll
-        for (int q = 0; q < NVZ; ++q) {
-            const int e = threadIdx.x + 512 * q;
-            const int r = e / (BM / VEC), c = (e % (BM / VEC)) * VEC;
-            rzh[q] = rzl[q] = make_uint4(0, 0, 0, 0);
-            if (s0 + r < s_end && m0 + c < a.M) {
-                const size_t o = (size_t)((s0 + r) * a.ldz + m0 + c);
-                rzh[q] = ld_as<uint4>(dzh + o);
-                rzl[q] = ld_as<uint4>(dzl + o);
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < NVF; ++q) {
-            const int e = threadIdx.x + 512 * q;
-            const int r = e / (BN / VEC), c = (e % (BN / VEC)) * VEC;
-            rfh[q] = rfl[q] = make_uint4(0, 0, 0, 0);
-            if (s0 + r < s_end && k0 + c < a.K) {
-                const size_t o = (size_t)((s0 + r) * a.ldf + k0 + c);
-                rfh[q] = ld_as<uint4>(fth + o);
-                rfl[q] = ld_as<uint4>(ftl + o);
-            }
-        }
-    };
-    auto store_stage = [&]() {
-#pragma unroll
-        for (int q = 0; q < NVZ; ++q) {
-            const int e = threadIdx.x + 512 * q;
-            const int r = e / (BM / VEC), c = (e % (BM / VEC)) * VEC;
-            st_as<uint4>(tzh + r * LDZ + c, rzh[q]);
-            st_as<uint4>(tzl + r * LDZ + c, rzl[q]);
-        }
-#pragma unroll
-        for (int q = 0; q < NVF; ++q) {
-            const int e = threadIdx.x + 512 * q;
-            const int r = e / (BN / VEC), c = (e % (BN / VEC)) * VEC;
-            st_as<uint4>(tfh + r * LDF + c, rfh[q]);
-            st_as<uint4>(tfl + r * LDF + c, rfl[q]);
-        }
-    };
-    auto tr_frag = [&](const T* tile, int ld, int r0, int c0) -> P::frag {
-        const u16* base = tile + r0 * ld + c0;
-        return frag_of<P::frag>(tr_read(base), tr_read(base + 4 * ld));
-    };
-
-    if (s_begin < s_end) load_stage(s_begin);
-    const int g = lane >> 4, gi = lane & 15, q4 = gi >> 2, p4 = gi & 3;
-    for (long long s0 = s_begin; s0 < s_end; s0 += SP) {
-        __syncthreads();  // previous stage fully consumed
-        store_stage();
-        __syncthreads();
-        if (s0 + SP < s_end) load_stage(s0 + SP);  // next stage in flight behind the MFMAs
-
-        if (do_bias) {
-            constexpr int RSTEP = 512 / BM > 0 ? 512 / BM : 1;
-            const int c = threadIdx.x % BM, r0 = threadIdx.x / BM;
-            if (r0 < RSTEP)
-                for (int r = r0; r < SP; r += RSTEP) bsum += bf2f(tzh[r * LDZ + c]) + bf2f(tzl[r * LDZ + c]);
-        }
-#pragma unroll
-        for (int ks = 0; ks < SP; ks += 16) {
-            const int r0 = ks + 8 * (g >> 1) + q4;  // this lane supplies row r0 (and r0 + 4)
-            P::frag zh[RT], zl[RT];
-#pragma unroll
-            for (int i = 0; i < RT; ++i) {
-                const int c0 = (wr * RT + i) * 32 + 16 * (g & 1) + 4 * p4;
-                zh[i] = tr_frag(tzh, LDZ, r0, c0);
-                zl[i] = tr_frag(tzl, LDZ, r0, c0);
-            }
-#pragma unroll
-            for (int j = 0; j < CT; ++j) {
-                const int c0 = (wc * CT + j) * 32 + 16 * (g & 1) + 4 * p4;
-                const P::frag fh = tr_frag(tfh, LDF, r0, c0), fl = tr_frag(tfl, LDF, r0, c0);
-#pragma unroll
-                for (int i = 0; i < RT; ++i) acc[i][j] = P::mma32(zh[i], fh, acc[i][j]);
-#pragma unroll
-                for (int i = 0; i < RT; ++i) acc[i][j] = P::mma32(zh[i], fl, acc[i][j]);
-#pragma unroll
-                for (int i = 0; i < RT; ++i) acc[i][j] = P::mma32(zl[i], fh, acc[i][j]);
-            }
-        }
-    }
-
-    float* out = a.partial + (size_t)chunk_id * a.M * a.K;
-#pragma unroll
-    for (int i = 0; i < RT; ++i)
-#pragma unroll
-        for (int j = 0; j < CT; ++j) {
-            const int k = k0 + (wc * CT + j) * 32 + (lane & 31);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + (wr * RT + i) * 32 + acc_row(lane, r);
-                if (m < a.M && k < a.K) out[(size_t)m * a.K + k] = acc[i][j][r];
-            }
-        }
-    if (do_bias) {
-        __syncthreads();
-        float* bs = reinterpret_cast<float*>(smem);
-        bs[threadIdx.x] = bsum;
-        __syncthreads();
-        constexpr int RSTEP = 512 / BM > 0 ? 512 / BM : 1;
-        if ((int)threadIdx.x < BM && m0 + (int)threadIdx.x < a.M) {
-            float s = 0.f;
-            for (int r = 0; r < RSTEP; ++r) s += bs[threadIdx.x + r * BM];
-            a.bpartial[(size_t)chunk_id * a.M + m0 + threadIdx.x] = s;
-        }
-    }
-}
-
-template <int RT, int CT, int SP>
-__global__ __launch_bounds__(512, 1) void k_wgrad_split(WgArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    wgrad_split_body<RT, CT, SP>(a, blockIdx.x, blockIdx.y, smem);
+    wgrad_body<P, RT, CT, SP, NPL>(a, blockIdx.x, blockIdx.y, smem);
 }
 
 // ---- bf16, 256 x 256 (or 256 x 96) output blocks: LDS-DMA ring
@@ -408,12 +278,11 @@ MARF_DEV void glds16(const char* src, unsigned lds) {
                  : "memory");
 }
 
-constexpr int F0_PATCHES = 4;  // patches a layer-0 weight-gradient chunk may span (host-checked)
 // Ring shapes (same-box A/B, profiles/r4g, r4h): the hidden layers read 32-row stages of dz + feat
 // through a 4-deep ring (64-row stages, a 5-deep ring and non-temporal loads measured no faster);
 // the layer-0 gradient, which recomputes feat_0 and moves only dz over the ring, runs 64-row stages
-// 3 deep (0.65 -> 0.53 ms at C3: half the barriers per pixel).
-constexpr int WG_SPH = 32, WG_NBUF_H = 4, WG_SP0 = 64, WG_NBUF_0 = 3, WG_NBUF_96 = 4;
+// 3 deep (0.65 -> 0.53 ms at C3: half the barriers per pixel).  (Stage heights WG_SPH, WG_SP0: marf_args.h)
+constexpr int WG_NBUF_H = 4, WG_NBUF_0 = 3, WG_NBUF_96 = 4;
 
 MARF_DEV int swz(int r, int c) {  // byte offset of bf16 element (r, c) in a 256-wide swizzled stage
     return r * 512 + ((((c >> 3) ^ (4 * (r & 3)))) << 4) + (c & 7) * 2;
@@ -434,8 +303,8 @@ MARF_DEV int foff(int r, int c) {
     else return r * (KF * 2) + c * 2;
 }
 
-// chunk `chunk_id` into output block `ob` (the body of one k_wgrad_dma block; also a work item of
-// k_wgrad_fused)
+// chunk `chunk_id` into output block `ob` (the body of one k_wgrad_dma block, and of one
+// k_wgrad_dma_layers block for its layer)
 // DZL (the hidden layer n-2 of a split-recipe step, T16, 256 wide, 32-row stages; a.dzl.g != null):
 // the dz half of a ring slot is not filled by LDS-DMA -- dz_{n-1} = relu'(z) (W_{n-1}^T g) is rebuilt
 // from what the step kernel stored in its place (marf_args.h DZL_G_SET ..), with the step kernel's device
@@ -1026,34 +895,68 @@ __global__ __launch_bounds__(256) void k_wgrad_reduce(const float* __restrict__ 
 
 using namespace marf;
 
-template <class P, int RT, int CT>
-static hipError_t launch_wg(const WgArgs& a, int n_chunks, int n_oblk, hipStream_t s) {
-    typedef typename P::T T;
-    constexpr int SP = 64;  // pixels per stage (128 measured slower: register pressure / spills)
-    constexpr int BM = WgGeo<RT, CT>::BM, BN = WgGeo<RT, CT>::BN;
-    constexpr int PADE = sizeof(T) == 2 ? 32 : 4;
-    size_t lds = (size_t)SP * (BM + PADE + BN + PADE) * sizeof(T);
-    if (lds < 512 * sizeof(float)) lds = 512 * sizeof(float);
-    {
-        hipError_t e = ensure_dynamic_lds((const void*)k_wgrad<P, RT, CT, SP>, lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((k_wgrad<P, RT, CT, SP>), dim3(n_chunks, n_oblk), dim3(512), lds, s, a);
-    return hipGetLastError();
+// f(P()) with P the arithmetic of dtype (0 fp32, 1 bf16, 2 fp16)
+template <class F>
+static hipError_t with_prec(int dtype, F f) {
+    return dtype == 1 ? f(PrecBF16()) : dtype == 2 ? f(PrecF16()) : f(PrecF32());
 }
 
-static bool wgrad_dma_enabled() {
+WgPick marf_wgrad_pick(const WgShape& w) {
     const char* e = getenv("MARF_WGRAD_DMA");  // A/B switch (read per launch): 0 = register-staged kernel
-    return !(e && e[0] == '0');
+    return wg_pick(w, !(e && e[0] == '0'));
+}
+
+// the pointers a job's kind needs beyond dz / feat / partial
+static bool wg_ptrs_ok(const WgJob& j) {
+    return (!j.split || (j.dz && j.dz_lo && j.feat && j.feat_lo)) && (!j.dzl || (j.dzl_src.g && j.dzl_src.mk && j.dzl_src.w)) &&
+           (!j.f0 || j.f0_geo);
+}
+
+// the kernels' argument record of a job on the kernel picked for it
+static WgArgs wg_args(const WgJob& j, const WgPick& pk) {
+    WgArgs a;
+    memset(&a, 0, sizeof(a));
+    a.dz = j.dz;
+    a.dz_lo = j.dz_lo;
+    a.feat = j.f0 ? nullptr : j.feat;
+    a.feat_lo = j.feat_lo;
+    if (j.f0) a.f0 = {*j.f0_geo, j.c2f_w, j.L, j.nk0};
+    a.S = j.S;
+    a.ldz = j.ldz;
+    a.ldf = j.f0 ? 96 : j.ldf;  // (f0: the 96-wide stage; K: the partial's columns, 96 or its first 64)
+    a.M = j.M;
+    a.K = j.K;
+    a.chunk = j.ranged ? WG_RANGE_CHUNK : j.chunk;
+    a.n_chunks = j.ranged ? j.rng.n : j.n_chunks;
+    a.n_oblk_c = (j.K + pk.bn - 1) / pk.bn;
+    a.partial = j.partial;
+    a.bpartial = j.bpartial;
+    if (j.ranged) {
+        a.s_lo = j.rng.s_lo;
+        a.s_len = j.rng.s_len;
+        a.rng_n = j.rng.n;
+        a.part0 = j.rng.part0;
+    }
+    a.t16 = j.t16 ? 1 : 0;
+    if (j.dzl) a.dzl = j.dzl_src;
+    return a;
+}
+
+// SP: pixels per stage (plain: 64; 128 measured slower: register pressure / spills)
+template <class P, int RT, int CT, int SP = 64, int NPL = 1>
+static hipError_t launch_wg(const WgArgs& a, int n_oblk, hipStream_t s) {
+    constexpr size_t lds = wg_staged_lds<typename P::T, RT, CT, SP, NPL>();
+    hipError_t e = ensure_dynamic_lds((const void*)k_wgrad<P, RT, CT, SP, NPL>, lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_wgrad<P, RT, CT, SP, NPL>), dim3(a.n_chunks, n_oblk), dim3(512), lds, s, a);
+    return hipGetLastError();
 }
 
 // LDS behind the hidden layers' ring when dz is recomputed: the sets' input slots and their sink
 constexpr size_t WG_DZL_LDS = (size_t)(WG_NBUF_H + 1) * (DZL_MK_SET + DZL_G_SET) + 256;
 
 template <class P, int KF, bool F0 = false, bool T16 = false, bool DZL = false>
-static hipError_t launch_wg_dma(WgArgs a, int n_chunks, hipStream_t s) {
-    a.n_chunks = n_chunks;
-    a.n_oblk_c = (a.K + KF - 1) / KF;
+static hipError_t launch_wg_dma(const WgArgs& a, hipStream_t s) {
     constexpr int SP = F0 ? WG_SP0 : KF == 256 ? WG_SPH : 32;
     constexpr int NBUF = KF == 256 ? WG_NBUF_H : F0 ? WG_NBUF_0 : WG_NBUF_96;  // ring depth within 160 KB of LDS
     const size_t lds = (size_t)NBUF * SP * (512 + KF * 2) + (KF == 256 ? 0 : 1024) + (F0 ? (9 * F0_PATCHES + 32 + (NBUF + 1) * SP * 2) * 4 : 0) +
@@ -1062,270 +965,122 @@ static hipError_t launch_wg_dma(WgArgs a, int n_chunks, hipStream_t s) {
         hipError_t e = ensure_dynamic_lds((const void*)k_wgrad_dma<P, NBUF, SP, KF, F0, T16, DZL>, lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL((k_wgrad_dma<P, NBUF, SP, KF, F0, T16, DZL>), dim3(n_chunks * (a.M / 256) * a.n_oblk_c), dim3(512), lds, s,
+    hipLaunchKernelGGL((k_wgrad_dma<P, NBUF, SP, KF, F0, T16, DZL>), dim3(a.n_chunks * (a.M / 256) * a.n_oblk_c), dim3(512), lds, s,
                        a);
     return hipGetLastError();
 }
 
-// Picks the output-block shape for an M x K weight gradient: 256x256 (2x4 tiles per wave),
-// 256x64 (2x1) or 128x64 (1x1).
-hipError_t marf_launch_wgrad(int dtype, const void* dz, int ldz, const void* feat, int ldf, long long S, int M, int K,
-                             int chunk, int n_chunks, float* partial, float* bpartial, hipStream_t s,
-                             const WgRange* rng, bool t16, const WgDzlSrc* dzl) {
-    WgArgs a;
-    memset(&a, 0, sizeof(a));
-    a.t16 = t16 ? 1 : 0;
-    if (dzl && dzl->g) {  // dz recomputed: the one shape marf_wgrad_dzl_ok takes, or an error
-        if (rng || dtype != 1 || !t16 || !dzl->mk || !dzl->w || !marf_wgrad_dzl_ok(M, ldz, K, ldf, S, chunk, n_chunks))
-            return hipErrorInvalidValue;
-        a.dzl = *dzl;
-    }
-    if (rng) {
-        a.s_lo = rng->s_lo;
-        a.s_len = rng->s_len;
-        a.rng_n = n_chunks = rng->n;
-        a.part0 = rng->part0;
-        chunk = 64;  // (a multiple of every stage height the range mode splits at)
-    }
-    a.dz = dz;
-    a.feat = feat;
-    a.S = S;
-    a.ldz = ldz;
-    a.ldf = ldf;
-    a.M = M;
-    a.K = K;
-    a.chunk = chunk;
-    a.partial = partial;
-    a.bpartial = bpartial;
-    int cfg;
-    if (M >= 256 && K >= 192) cfg = 0;       // 256 x 256 (2 x 4 tiles per wave)
-    else if (M >= 256 && K > 64) cfg = 3;    // 256 x 128 (2 x 2): layer 0 at L = 16 reads dz once
-    else if (M >= 256) cfg = 1;              // 256 x 64  (2 x 1)
-    else cfg = 2;                            // 128 x 64  (1 x 1)
-    int BM = cfg == 2 ? 128 : 256, BN = cfg == 0 ? 256 : (cfg == 3 ? 128 : 64);
-    int nr = (M + BM - 1) / BM, nc = (K + BN - 1) / BN;
-    a.n_oblk_c = nc;
-    // LDS-DMA ring: 256-wide dz with a 256-wide (hidden) or 96-wide (layer 0, L = 16) feat
-    const bool dma = M % 256 == 0 && ldz % 8 == 0 && ldz >= M && S % 32 == 0 && chunk % 32 == 0 &&
-                     (long long)n_chunks * (M / 256) * ((K + 255) / 256) <= 0x7fffffff && wgrad_dma_enabled();
-    const bool dma256 = dma && K % 256 == 0 && ldf % 8 == 0 && ldf >= K && S % WG_SPH == 0 && chunk % WG_SPH == 0,
-               dma96 = dma && K == 96 && ldf == 96;
-    if (rng && (dtype == 0 || !(dma256 || dma96))) return hipErrorInvalidValue;  // range mode: LDS-DMA kernel only
-    if (t16 && dtype == 0) return hipErrorInvalidValue;  // (T16: 16-bit tensors of the step kernel only)
-    if (dtype == 1) {
-        if (a.dzl.g) return launch_wg_dma<PrecBF16, 256, false, true, true>(a, n_chunks, s);
-        if (dma256) return t16 ? launch_wg_dma<PrecBF16, 256, false, true>(a, n_chunks, s) : launch_wg_dma<PrecBF16, 256>(a, n_chunks, s);
-        if (dma96) return t16 ? launch_wg_dma<PrecBF16, 96, false, true>(a, n_chunks, s) : launch_wg_dma<PrecBF16, 96>(a, n_chunks, s);
-        if (cfg == 0) return launch_wg<PrecBF16, 2, 4>(a, n_chunks, nr * nc, s);
-        if (cfg == 3) return launch_wg<PrecBF16, 2, 2>(a, n_chunks, nr * nc, s);
-        if (cfg == 1) return launch_wg<PrecBF16, 2, 1>(a, n_chunks, nr * nc, s);
-        return launch_wg<PrecBF16, 1, 1>(a, n_chunks, nr * nc, s);
-    }
-    if (dtype == 2) {
-        if (dma256) return t16 ? launch_wg_dma<PrecF16, 256, false, true>(a, n_chunks, s) : launch_wg_dma<PrecF16, 256>(a, n_chunks, s);
-        if (dma96) return t16 ? launch_wg_dma<PrecF16, 96, false, true>(a, n_chunks, s) : launch_wg_dma<PrecF16, 96>(a, n_chunks, s);
-        if (cfg == 0) return launch_wg<PrecF16, 2, 4>(a, n_chunks, nr * nc, s);
-        if (cfg == 3) return launch_wg<PrecF16, 2, 2>(a, n_chunks, nr * nc, s);
-        if (cfg == 1) return launch_wg<PrecF16, 2, 1>(a, n_chunks, nr * nc, s);
-        return launch_wg<PrecF16, 1, 1>(a, n_chunks, nr * nc, s);
-    }
-    if (cfg == 0) return launch_wg<PrecF32, 2, 4>(a, n_chunks, nr * nc, s);
-    if (cfg == 3) return launch_wg<PrecF32, 2, 2>(a, n_chunks, nr * nc, s);
-    if (cfg == 1) return launch_wg<PrecF32, 2, 1>(a, n_chunks, nr * nc, s);
-    return launch_wg<PrecF32, 1, 1>(a, n_chunks, nr * nc, s);
-}
-
-// 256 x 256 output blocks (2 x 4 tiles per wave), 32-pixel stages: four tiles of 32 x 288 bf16 = 72 KB.
-// The mask net's layer 0 (K = 448) takes two column blocks, the second 192 wide.
-hipError_t marf_launch_wgrad_split(const void* dz_hi, const void* dz_lo, int ldz, const void* feat_hi,
-                                   const void* feat_lo, int ldf, long long S, int M, int K, int chunk, int n_chunks,
-                                   float* partial, float* bpartial, hipStream_t s) {
-    constexpr int RT = 2, CT = 4, SP = 32;
-    constexpr int BM = WgGeo<RT, CT>::BM, BN = WgGeo<RT, CT>::BN;
-    if (!dz_hi || !dz_lo || !feat_hi || !feat_lo || ldz % 8 || ldf % 8 || chunk % SP || n_chunks < 1)
-        return hipErrorInvalidValue;
-    WgArgs a;
-    memset(&a, 0, sizeof(a));
-    a.dz = dz_hi;
-    a.dz_lo = dz_lo;
-    a.feat = feat_hi;
-    a.feat_lo = feat_lo;
-    a.S = S;
-    a.ldz = ldz;
-    a.ldf = ldf;
-    a.M = M;
-    a.K = K;
-    a.chunk = chunk;
-    a.n_chunks = n_chunks;
-    a.partial = partial;
-    a.bpartial = bpartial;
-    const int nr = (M + BM - 1) / BM, nc = (K + BN - 1) / BN;
-    a.n_oblk_c = nc;
-    const size_t lds = (size_t)SP * 2 * (BM + 32 + BN + 32) * 2;
-    hipError_t e = ensure_dynamic_lds((const void*)k_wgrad_split<RT, CT, SP>, lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_wgrad_split<RT, CT, SP>), dim3(n_chunks, nr * nc), dim3(512), lds, s, a);
-    return hipGetLastError();
-}
-
-// The range mode (WgRange) runs on the LDS-DMA kernel only: true if an M x K gradient with these
-// strides takes it (bf16 / fp16; marf_launch_wgrad's dma256 / dma96 conditions).
-bool marf_wgrad_range_ok(int dtype, int M, int ldz, int K, int ldf) {
-    if (dtype != 1 && dtype != 2) return false;
-    if (!(M % 256 == 0 && ldz % 8 == 0 && ldz >= M && wgrad_dma_enabled())) return false;
-    return (K % 256 == 0 && ldf % 8 == 0 && ldf >= K) || (K == 96 && ldf == 96);
-}
-
-bool marf_wgrad_dzl_ok(int M, int ldz, int K, int ldf, long long S, int chunk, int n_chunks) {
-    return M == 256 && K == 256 && ldz == 256 && ldf % 8 == 0 && ldf >= K && S % WG_SPH == 0 && chunk % WG_SPH == 0 &&
-           n_chunks >= 1 && wgrad_dma_enabled();
-}
-
-// Layer-0 weight gradient with feat_0 recomputed on chip (step kernel's feat0_recompute); bf16,
-// 256-wide layer 0, the 64-wide feat_0 of L <= 12 or the 96-wide one of L = 13..16 (both built in
-// the 96-wide stage, whose 192-B rows keep the transposed reads conflict-free; a 64-wide partial
-// takes its first 64 columns).  False if the shape does not qualify.  L <= 16: the stage's 16
-// threads per row build two bands of one coordinate each, so bands 16..19 of L = 17..20 (whose
-// feat_0 is 96 wide too: columns 64..79) would stay unwritten; those nets store and read feat_0.
-bool marf_wgrad_l0_recompute_ok(int M, int ldz, int ldf0, int L, long long S, int chunk, int n_chunks,
-                                long long Np_pad) {
-    return M == 256 && ldz % 8 == 0 && ldz >= M && (ldf0 == 96 || ldf0 == 64) && L <= 16 && S % WG_SP0 == 0 &&
-           chunk % WG_SP0 == 0 &&
-           (long long)n_chunks <= 0x7fffffff && Np_pad < (1 << 24) && (chunk + Np_pad - 1) / Np_pad + 1 <= F0_PATCHES;
-}
-
-hipError_t marf_launch_wgrad_l0_recompute(const void* dz, int ldz, const GeoDev& geo, const float* c2f_w, int L,
-                                          int nk0, int K0, long long S, int M, int chunk, int n_chunks, float* partial,
-                                          float* bpartial, hipStream_t s, const WgRange* rng, int dtype) {
-    WgArgs a;
-    memset(&a, 0, sizeof(a));
-    if (L > 16 || (K0 != 96 && K0 != 64)) return hipErrorInvalidValue;  // (marf_wgrad_l0_recompute_ok)
-    if (rng) {
-        a.s_lo = rng->s_lo;
-        a.s_len = rng->s_len;
-        a.rng_n = n_chunks = rng->n;
-        a.part0 = rng->part0;
-    }
-    a.dz = dz;
-    a.feat = nullptr;
-    a.f0.geo = geo;
-    a.f0.c2f_w = c2f_w;
-    a.f0.L = L;
-    a.f0.nk0 = nk0;
-    a.S = S;
-    a.ldz = ldz;
-    a.ldf = 96;
-    a.M = M;
-    a.K = K0;  // partial columns: 96, or the first 64 of the 96-wide stage
-    a.t16 = 1;  // dz_1 from the step kernel
-    a.chunk = chunk;
-    a.partial = partial;
-    a.bpartial = bpartial;
-    // (dtype 2: the fp16x2 recipe's dz_1 and feat_0 in fp16)
-    if (dtype == 2) return launch_wg_dma<PrecF16, 96, true, true>(a, n_chunks, s);
-    return launch_wg_dma<PrecBF16, 96, true, true>(a, n_chunks, s);
+hipError_t marf_launch_wgrad(const WgJob& j, hipStream_t s) {
+    const WgPick pk = marf_wgrad_pick(j);
+    if (pk.k == WG_NONE || !wg_ptrs_ok(j)) return hipErrorInvalidValue;
+    const WgArgs a = wg_args(j, pk);
+    const int nb = pk.blocks(j);
+    return with_prec(j.dtype, [&](auto prec) -> hipError_t {
+        typedef decltype(prec) P;
+        constexpr bool bf16 = std::is_same<P, PrecBF16>::value;
+        if constexpr (sizeof(typename P::T) == 2) {  // the LDS-DMA kernels: bf16 / fp16 (fp16x2's saved tensors)
+            switch (pk.k) {
+                case WG_DMA256: return j.t16 ? launch_wg_dma<P, 256, false, true>(a, s) : launch_wg_dma<P, 256>(a, s);
+                case WG_DMA96: return j.t16 ? launch_wg_dma<P, 96, false, true>(a, s) : launch_wg_dma<P, 96>(a, s);
+                case WG_DMA_F0: return launch_wg_dma<P, 96, true, true>(a, s);  // (dz_1 from the step kernel: T16)
+                default: break;
+            }
+        }
+        if constexpr (bf16) {
+            if (pk.k == WG_DMA_DZL) return launch_wg_dma<P, 256, false, true, true>(a, s);
+            // 32-pixel stages: four tiles of 32 x 288 bf16 = 72 KB
+            if (pk.k == WG_STAGED_SPLIT) return launch_wg<P, 2, 4, 32, 2>(a, nb, s);
+        }
+        if (pk.k != WG_STAGED) return hipErrorInvalidValue;
+        if (pk.bn == 256) return launch_wg<P, 2, 4>(a, nb, s);
+        if (pk.bn == 128) return launch_wg<P, 2, 2>(a, nb, s);
+        return pk.bm == 256 ? launch_wg<P, 2, 1>(a, nb, s) : launch_wg<P, 1, 1>(a, nb, s);
+    });
 }
 
 // ---- the fused launch: hidden layers in one launch, layer 0 beside it on `s2`, one reduction launch
-bool marf_wgrad_fused_ok(const WgFusedLayer* layers, int n_layers, long long S, int chunk, int n_chunks,
-                         long long Np_pad, int L_bands) {
-    if (!layers || n_layers < 1 || n_layers > WF_MAXJ || n_chunks < 1 || chunk < 64 || chunk % 64) return false;
+
+// a product that runs as a layer of k_wgrad_dma_layers: one 256 x 256 block of T16 tensors
+static bool wg_in_layers(const WgJob& j, const WgPick& pk) {
+    return (pk.k == WG_DMA256 || pk.k == WG_DMA_DZL) && j.t16 && pk.blocks(j) == 1;
+}
+
+bool marf_wgrad_fused_ok(const WgFusedLayer* layers, int n_layers) {
+    if (!layers || n_layers < 1 || n_layers > WF_MAXJ) return false;
     if (const char* e = getenv("MARF_WGRAD_FUSED")) {  // A/B switch (read per launch): 0 = per-layer launches
         if (e[0] == '0') return false;
     }
-    int n_l0 = 0;
+    // At most one product may stand outside the layers' launch.  That is layer 0: a product in it needs
+    // one 256 x 256 block, feat_0 is at most 96 wide, and a hidden layer that does not fit makes two.
+    const WgJob* first = nullptr;  // the products share one split of the pixel rows
+    int n_side = 0;
     for (int i = 0; i < n_layers; ++i) {
         const WgFusedLayer& L = layers[i];
-        if (L.Mo > L.M || L.Ko > L.K || !L.partial || !L.bpartial || !L.dW || !L.db) return false;
-        switch (L.kind) {
-            case 0:  // k_wgrad_dma<PrecBF16, 4, 32, 256>'s one-output-block shape (marf_launch_wgrad's dma256)
-                if (!(L.M == 256 && L.K == 256 && L.ldz % 8 == 0 && L.ldz >= L.M && L.ldf % 8 == 0 && L.ldf >= L.K &&
-                      S % WG_SPH == 0 && chunk % WG_SPH == 0 && wgrad_dma_enabled()))
-                    return false;
-                break;
-            case 1:  // marf_launch_wgrad_l0_recompute's shape
-                if (!marf_wgrad_l0_recompute_ok(L.M, L.ldz, L.K, L_bands, S, chunk, n_chunks, Np_pad)) return false;
-                ++n_l0;
-                break;
-            case 2:  // layer 0 stored: any shape marf_launch_wgrad takes (its kernel is picked there)
-                ++n_l0;
-                break;
-            case 3:
-                if (L.n_parts < 1 || L.n_parts > 1024) return false;  // (the per-layer path folds above 1024)
-                break;
-            default: return false;
+        const WgJob& j = L.job;
+        if (L.Mo > j.M || L.Ko > j.K || !j.partial || !j.bpartial || !L.dW || !L.db) return false;
+        if (!j.dz) {  // reduction only
+            if (L.n_parts < 1 || L.n_parts > 1024) return false;  // (the per-layer path folds above 1024)
+            continue;
         }
+        if (!first) first = &j;
+        if (j.ranged || j.n_chunks < 1 || j.chunk < 64 || j.chunk % 64 || L.n_parts != j.n_chunks || j.S != first->S ||
+            j.chunk != first->chunk || j.n_chunks != first->n_chunks || j.dtype != first->dtype)
+            return false;
+        const WgPick pk = marf_wgrad_pick(j);
+        if (pk.k == WG_NONE) return false;
+        n_side += !wg_in_layers(j, pk);
     }
-    return n_l0 <= 1;
+    return n_side <= 1;
 }
 
-hipError_t marf_launch_wgrad_fused(const WgFusedLayer* layers, int n_layers, long long S, int chunk, int n_chunks,
-                                   const GeoDev& f0_geo, const float* c2f_w, int L, int nk0, const float* gscale,
-                                   const float* denom, hipStream_t s, hipStream_t s2, hipEvent_t fork,
-                                   hipEvent_t join, int dtype, float post) {
+hipError_t marf_launch_wgrad_fused(const WgFusedLayer* layers, int n_layers, const float* gscale, const float* denom,
+                                   hipStream_t s, hipStream_t s2, hipEvent_t fork, hipEvent_t join, float post) {
     hipError_t e;
-    // layer 0 on s2, beside the hidden layers
-    const WgFusedLayer* l0 = nullptr;
-    for (int i = 0; i < n_layers; ++i)
-        if (layers[i].kind == 1 || layers[i].kind == 2) l0 = &layers[i];
-    if (l0) {
-        if ((e = hipEventRecord(fork, s)) != hipSuccess || (e = hipStreamWaitEvent(s2, fork, 0)) != hipSuccess) return e;
-        if (l0->kind == 1)
-            e = marf_launch_wgrad_l0_recompute(l0->dz, l0->ldz, f0_geo, c2f_w, L, nk0, l0->K, S, l0->M, chunk, n_chunks, l0->partial,
-                                               l0->bpartial, s2, nullptr, dtype);
-        else
-            e = marf_launch_wgrad(dtype, l0->dz, l0->ldz, l0->feat, l0->ldf, S, l0->M, l0->K, chunk, n_chunks, l0->partial,
-                                  l0->bpartial, s2, nullptr, true);
-        if (e != hipSuccess) return e;
-        if ((e = hipEventRecord(join, s2)) != hipSuccess) return e;
-    }
-    // every hidden layer's chunks: one launch, layer-major blocks
+    // every hidden layer's chunks: one launch, layer-major blocks; layer 0 on s2, beside them
     WgLayersArgs la;
     memset(&la, 0, sizeof(la));
-    la.n_chunks = n_chunks;
-    int nh = 0;
+    const WgJob* side = nullptr;
+    int nh = 0, dtype = 1;
     bool any_dzl = false;
     for (int i = 0; i < n_layers; ++i) {
-        const WgFusedLayer& Ly = layers[i];
-        if (Ly.kind != 0) continue;
-        WgArgs& a = la.a[nh++];
-        a.dz = Ly.dz;
-        a.feat = Ly.feat;
-        a.S = S;
-        a.ldz = Ly.ldz;
-        a.ldf = Ly.ldf;
-        a.M = Ly.M;
-        a.K = Ly.K;
-        a.chunk = chunk;
-        a.n_chunks = n_chunks;
-        a.n_oblk_c = 1;
-        a.partial = Ly.partial;
-        a.bpartial = Ly.bpartial;
-        a.t16 = 1;
-        if (Ly.dzl.g) {  // (layer n-2: dz recomputed)
-            if (dtype != 1 || !Ly.dzl.mk || !Ly.dzl.w || !marf_wgrad_dzl_ok(Ly.M, Ly.ldz, Ly.K, Ly.ldf, S, chunk, n_chunks))
-                return hipErrorInvalidValue;
-            a.dzl = Ly.dzl;
-            any_dzl = true;
+        const WgJob& j = layers[i].job;
+        if (!j.dz) continue;
+        const WgPick pk = marf_wgrad_pick(j);
+        if (!wg_in_layers(j, pk)) {
+            side = &j;
+            continue;
         }
+        if (!wg_ptrs_ok(j)) return hipErrorInvalidValue;
+        la.a[nh++] = wg_args(j, pk);
+        la.n_chunks = j.n_chunks;
+        dtype = j.dtype;
+        any_dzl |= j.dzl;  // (layer n-2: dz recomputed)
+    }
+    if (side) {
+        if ((e = hipEventRecord(fork, s)) != hipSuccess || (e = hipStreamWaitEvent(s2, fork, 0)) != hipSuccess) return e;
+        if ((e = marf_launch_wgrad(*side, s2)) != hipSuccess) return e;
+        if ((e = hipEventRecord(join, s2)) != hipSuccess) return e;
     }
     if (nh) {
-        const size_t lds = (size_t)WG_NBUF_H * WG_SPH * (512 + 256 * 2);
-        auto go = [&](auto prec, auto dzl_tag) -> hipError_t {
+        e = with_prec(dtype, [&](auto prec) -> hipError_t {
             typedef decltype(prec) P;
-            constexpr bool DZL = decltype(dzl_tag)::value;
-            const size_t ldsx = lds + (DZL ? WG_DZL_LDS : 0);
-            hipError_t er = ensure_dynamic_lds((const void*)k_wgrad_dma_layers<P, WG_NBUF_H, WG_SPH, 256, DZL>, ldsx);
-            if (er != hipSuccess) return er;
-            hipLaunchKernelGGL((k_wgrad_dma_layers<P, WG_NBUF_H, WG_SPH, 256, DZL>), dim3(nh * n_chunks), dim3(512), ldsx, s, la);
-            return hipGetLastError();
-        };
-        // (fp16x2: fp16 saved tensors)
-        e = dtype == 2 ? go(PrecF16(), std::false_type())
-                       : (any_dzl ? go(PrecBF16(), std::true_type()) : go(PrecBF16(), std::false_type()));
+            auto go = [&](auto dzl_tag) -> hipError_t {
+                constexpr bool DZL = decltype(dzl_tag)::value;
+                const size_t lds = (size_t)WG_NBUF_H * WG_SPH * (512 + 256 * 2) + (DZL ? WG_DZL_LDS : 0);
+                hipError_t er = ensure_dynamic_lds((const void*)k_wgrad_dma_layers<P, WG_NBUF_H, WG_SPH, 256, DZL>, lds);
+                if (er != hipSuccess) return er;
+                hipLaunchKernelGGL((k_wgrad_dma_layers<P, WG_NBUF_H, WG_SPH, 256, DZL>), dim3(nh * la.n_chunks), dim3(512), lds, s, la);
+                return hipGetLastError();
+            };
+            if constexpr (sizeof(typename P::T) == 2) {  // (fp16: the fp16x2 recipe's saved tensors)
+                if (!any_dzl) return go(std::false_type());
+                if constexpr (std::is_same<P, PrecBF16>::value) return go(std::true_type());
+            }
+            return hipErrorInvalidValue;
+        });
         if (e != hipSuccess) return e;
     }
-    if (l0 && (e = hipStreamWaitEvent(s, join, 0)) != hipSuccess) return e;
+    if (side && (e = hipStreamWaitEvent(s, join, 0)) != hipSuccess) return e;
     // every layer's reduction: one launch, in the layers' order
     WgRedArgs r;
     memset(&r, 0, sizeof(r));
@@ -1335,19 +1090,9 @@ hipError_t marf_launch_wgrad_fused(const WgFusedLayer* layers, int n_layers, lon
     int blk = 0;
     for (int i = 0; i < n_layers; ++i) {
         const WgFusedLayer& Ly = layers[i];
-        WgRedJob& q = r.job[i];
-        q.partial = Ly.partial;
-        q.bpartial = Ly.bpartial;
-        q.n_chunks = Ly.kind == 3 ? Ly.n_parts : n_chunks;
-        q.M = Ly.M;
-        q.K = Ly.K;
-        q.Mo = Ly.Mo;
-        q.Ko = Ly.Ko;
-        q.dW = Ly.dW;
-        q.db = Ly.db;
-        q.kmap = Ly.kmap;
-        q.post = Ly.kind == 3 ? 1.f : post;  // (the last layer's partials: unscaled in the step kernel)
-        q.blk0 = blk;
+        // (a reduction-only layer, the last: its partials are unscaled in the step kernel)
+        r.job[i] = {Ly.job.partial, Ly.job.bpartial, Ly.n_parts, Ly.job.M, Ly.job.K, Ly.Mo, Ly.Ko, blk, Ly.dW, Ly.db, Ly.kmap,
+                    Ly.job.dz ? post : 1.f};
         blk += (int)(((long long)Ly.Mo * Ly.Ko + Ly.Mo + 63) / 64);
     }
     hipLaunchKernelGGL(k_wgrad_reduce_layers, dim3(blk), dim3(256), 0, s, r);
@@ -1356,16 +1101,11 @@ hipError_t marf_launch_wgrad_fused(const WgFusedLayer* layers, int n_layers, lon
 
 hipError_t marf_launch_wgrad_last(int dtype, const float* glast, const void* feat, long long S, int ldf, int K, int chunk,
                                   int n_chunks, float* partial, float* bpartial, hipStream_t s) {
-    if (dtype == 1)
-        hipLaunchKernelGGL(k_wgrad_last<PrecBF16>, dim3(n_chunks), dim3(256), 0, s, glast, feat, S, ldf, K, chunk,
+    return with_prec(dtype, [&](auto prec) -> hipError_t {
+        hipLaunchKernelGGL(k_wgrad_last<decltype(prec)>, dim3(n_chunks), dim3(256), 0, s, glast, feat, S, ldf, K, chunk,
                            partial, bpartial);
-    else if (dtype == 2)
-        hipLaunchKernelGGL(k_wgrad_last<PrecF16>, dim3(n_chunks), dim3(256), 0, s, glast, feat, S, ldf, K, chunk,
-                           partial, bpartial);
-    else
-        hipLaunchKernelGGL(k_wgrad_last<PrecF32>, dim3(n_chunks), dim3(256), 0, s, glast, feat, S, ldf, K, chunk,
-                           partial, bpartial);
-    return hipGetLastError();
+        return hipGetLastError();
+    });
 }
 
 hipError_t marf_launch_wgrad_reduce(const float* partial, const float* bpartial, int n_chunks, int M, int K, int Mo,

@@ -16,6 +16,12 @@ The split-*, plain-fwd-bwd, render-* and mask-* cases ("tile_view_cases" in the 
 parent commit) pin what had no bit fixture before the tile phases were written once over a tile view:
 the split tile step k_mlp_step_split and its render, the separate k_mlp_fwd / k_mlp_bwd path and the
 mask network's kernels in both recipes.  Kept on the same rule; none had to be left out.
+
+The wg-* cases ("wgrad_cases" in the fixture, with their parent commit) reach the weight-gradient
+paths that no case above does: the per-layer launches of the LDS-DMA kernel with and without its
+recomputing instantiations, the register-staged kernel on T16 tensors, range mode (the pipelined
+step), more than one output block per chunk under both block maps, and fp32 fragments in 128 x 64
+blocks.  Same rule (the parent library, three separate processes); none had to be left out.
 """
 import hashlib
 import os
@@ -31,6 +37,8 @@ BITS_JSON = os.path.join(HERE, "golden", "step2_sched_bits.json")
 DEV = step_bits.DEV
 
 FULL = [256] * 4
+# per-layer weight-gradient launches that read feat_0 and dz_{n-1} as the step kernel stored them
+_STORED = {"MARF_WGRAD_FUSED": "0", "MARF_F0_RECOMPUTE": "0", "MARF_DZL_RECOMPUTE": "0"}
 CASES = {
     # name: (patches, patch_H, patch_W, L, hidden widths, environment, model options)
     # 32 tiles on 3 blocks (11, 11, 10 tiles): (5, 3) instantiation
@@ -68,6 +76,24 @@ CASES = {
     # of test_gpu_parity.py pinned their bits: its fused-against-separate test compares two paths of
     # one build
     "plain-fwd-bwd": (1, 64, 64, 8, FULL, {}, {"precision": "bf16", "fused_step": False}),
+    # ---- the weight-gradient paths no case above reaches ("wgrad_cases" in the fixture)
+    # the per-layer launches of the LDS-DMA kernel, its DZL and F0 instantiations among them
+    "wg-perlayer": (1, 64, 64, 16, FULL, {"MARF_WGRAD_FUSED": "0"}, {}),
+    # ... on stored T16 tensors: the 96-wide layer 0 and the 256-wide hidden layers
+    "wg-stored": (1, 64, 64, 16, FULL, _STORED, {}),
+    # ... and with the register-staged kernel reading T16 (t16_off), at 256 x 256 and 256 x 128
+    "wg-staged-t16": (1, 64, 64, 16, FULL, dict(_STORED, MARF_WGRAD_DMA="0"), {}),
+    # range mode: 2 x 17 tiles of 128 slots in pieces of 12 tiles -> 12, 12 and 10 tiles; 16 blocks
+    # per piece (3 stages of 32 rows each), every CU's block on the last, shorter one
+    "wg-ranged": (2, 40, 52, 16, FULL, {"MARF_PIPE": "1", "MARF_PIPE_WG": "16", "MARF_PIPE_PIECE": "12"}, {}),
+    # k_wgrad_dma with 2 x 2 output blocks per chunk.  split_k: 2 patches of 2,080 pixels padded to the
+    # tile give S = 4,224 (64-pixel tiles) or 4,352 (128), chunk 64, 66 or 68 chunks -- no multiple of
+    # 8: the plain block map (block -> chunk block % n_chunks)
+    "wg-wide-bf16": (2, 40, 52, 8, [512, 512], {}, {"precision": "bf16"}),
+    # S = 4,096, chunk 64, 64 chunks -- a multiple of 8: the XCD-grouped block map
+    "wg-wide-bf16-x8": (1, 64, 64, 8, [512, 512], {}, {"precision": "bf16"}),
+    # fp32 fragments in 128 x 64 output blocks (M = 128 and M = 96)
+    "wg-fp32-narrow": (1, 64, 64, 8, [128, 96, 128], {}, {"precision": "fp32"}),
 }
 # the FWD instantiation of k_mlp_step_split: Model.predict_entire_image of the 6 x 128 net on a
 # 45 x 61 canvas (2,745 pixels: no multiple of 128)
