@@ -122,6 +122,33 @@ static WgJob wg_job(const WgShape& w, const void* dz, const void* feat, float* p
     return j;
 }
 
+// A net's weight gradients as a WgLayer list in the order a backward finishes them: 0 .. n-1, or
+// (last_first, the step backwards: a bucketed all-reduce of finished layers overlaps the remaining
+// products) the last layer, then n-2 .. 0.  Filled here, for the image net and the mask net: what the
+// net alone decides -- each entry's layer, its true shape Mo x Ko (kin: a skip layer's input included)
+// and where dW / db lie in the flat gradient.  A site adds its own: products or partials, part counts.
+static void wg_layers(const NetShape& n, float* dparams, bool last_first, WgLayer* out) {
+    memset(out, 0, sizeof(WgLayer) * n.n_layers);
+    for (int i = 0; i < n.n_layers; ++i) {
+        WgLayer& x = out[i];
+        x.l = last_first ? n.n_layers - 1 - i : i;
+        x.Mo = n.dims[x.l + 1];
+        x.Ko = n.kin[x.l];
+        x.dW = dparams + n.w_off[x.l];
+        x.db = dparams + n.b_off[x.l];
+    }
+}
+// the last layer of a step: no product, the step kernel left n_parts partials [3][K] (one per block or
+// tile); above 1,024 of them the reduction folds them into `scratch` first
+static void wg_step_last(WgLayer& x, const char* wlast, const char* blast, int n_parts, int K, float* scratch) {
+    x.job.partial = (float*)wlast;
+    x.job.bpartial = (float*)blast;
+    x.job.M = 3;
+    x.job.K = K;
+    x.n_parts = n_parts;
+    x.scratch = scratch;
+}
+
 // W_l then b_l in the flat parameter vector; Wf_l, Wt_l, bias_l in the packed buffer (pelem: bytes
 // per packed weight).  dims, kin, Kp, Mp, Mt are set.
 static void plan_params(NetShape& n, int pelem) {
@@ -800,6 +827,88 @@ static int launch_warp_bwd(const float* dH_partial, int per_patch, const GeoDev&
     return MARF_OK;
 }
 
+// record layer l's "gradient final" event, if the caller passed one
+static int mark_layer(const void* const* ev, int l, hipStream_t s) {
+    if (ev && ev[l]) HIPCHK(hipEventRecord((hipEvent_t)ev[l], s), "step_backward: layer event");
+    return MARF_OK;
+}
+
+// The profile scopes of a list's launches (null: that launch runs under none).  String literals:
+// marf_prof.hip keeps the pointer until the next read.
+struct WgScopes {
+    const char *l0, *hidden, *reduce, *last, *last_reduce;
+};
+static const WgScopes k_wg_scopes = {"wgrad_l0", "wgrad_hidden", "wgrad_reduce", "wgrad_last", nullptr};
+static const WgScopes k_wg_step_scopes = {"wgrad_l0", "wgrad_hidden", "wgrad_reduce", nullptr, "wgrad_last_reduce"};
+static const WgScopes k_mask_wg_scopes = {"mask_wgrad_l0", "mask_wgrad_hidden", "mask_wgrad_reduce", "mask_wgrad_last",
+                                          nullptr};
+
+// The per-layer weight gradients: the list in its order, per entry its product (if it has one), its
+// reduction and its layer's event (ev null: none).  gscale / denom: a step's upstream gradient and
+// loss denominator; post: the scale of the entries with a product (marf_launch_wgrad_fused);
+// who: the entry point, in front of an error's text.
+static int run_wg_layers(const WgLayer* layers, int n, const WgScopes& sc, const float* gscale, const float* denom,
+                         float post, const void* const* ev, hipStream_t s, const char* who) {
+    for (int i = 0; i < n; ++i) {
+        const WgLayer& x = layers[i];
+        const WgJob& j = x.job;
+        if (x.glast || j.dz) {
+            const char* name = x.glast ? sc.last : x.l == 0 ? sc.l0 : sc.hidden;
+            void* prof = name ? marf_prof_begin(name, s) : nullptr;
+            const hipError_t e = x.glast ? marf_launch_wgrad_last(j.dtype, x.glast, j.feat, j.S, j.ldf, j.K, j.chunk,
+                                                                  j.n_chunks, j.partial, j.bpartial, s)
+                                         : marf_launch_wgrad(j, s);
+            marf_prof_end(prof, s);
+            if (e != hipSuccess)
+                return fail(MARF_ERR_HIP, "%s wgrad of layer %d%s: %s", who, x.l, j.f0 ? " (feat_0 recomputed)" : "",
+                            hipGetErrorString(e));
+        }
+        const char* name = x.l == n - 1 ? sc.last_reduce : sc.reduce;
+        void* prof = name ? marf_prof_begin(name, s) : nullptr;
+        const hipError_t e = marf_launch_wgrad_reduce(j.partial, j.bpartial, x.n_parts, j.M, j.K, x.Mo, x.Ko, x.dW, x.db, s,
+                                                      gscale, denom, x.scratch, x.kmap, j.dz ? post : 1.f);
+        marf_prof_end(prof, s);
+        if (e != hipSuccess) return fail(MARF_ERR_HIP, "%s wgrad reduce of layer %d: %s", who, x.l, hipGetErrorString(e));
+        const int rc = mark_layer(ev, x.l, s);
+        if (rc) return rc;
+    }
+    return MARF_OK;
+}
+
+// The list of an unfused backward (marf_backward, marf_mask_backward), layers 0 .. n-1: dz_{l+1} from
+// the workspace (x) the saved feat_l into the workspace's one partial buffer, the last layer from
+// glast on its finer split.  split: the mask net's MARF_BF16X3A, each operand a hi and a lo plane.
+static void wg_unfused_layers(const NetShape& n, long long S, const SavedPlan& sp, const WsPlan& wp, const char* sv,
+                              char* ws, float* dparams, bool split, WgLayer* out) {
+    float* part = (float*)(ws + wp.part);
+    float* bpart = (float*)(ws + wp.bpart);
+    const int last = n.n_layers - 1;
+    wg_layers(n, dparams, false, out);
+    for (int l = 0; l < last; ++l) {
+        WgJob& w = out[l].job;
+        w = wg_job(wg_shape(n, l, S, wp.k), ws + wp.dz[l + 1], sv + sp.feat[l], part, bpart);
+        if (split) {  // hi plane [S][Kp], the lo plane behind it
+            w.split = true;
+            w.dz_lo = (const char*)w.dz + (size_t)S * n.Kp[l + 1] * 2;
+            w.feat_lo = (const char*)w.feat + (size_t)S * n.Kp[l] * 2;
+        }
+        out[l].n_parts = wp.k.n;
+    }
+    // (the image net's Mo = 3 fills the partial's three rows; the mask net's glast rows 1..3 are zero
+    //  and its Mo = 1: row 0 of the 3-row partial is the one real output row)
+    WgLayer& x = out[last];
+    x.glast = (const float*)(ws + wp.glast);
+    x.job.dtype = split ? 0 : n.kdt;  // (split: feat_{n-1} was saved as fp32, float(hi) + float(lo))
+    x.job.feat = sv + sp.feat[last];
+    x.job.partial = part;
+    x.job.bpartial = bpart;
+    x.job.S = S;
+    x.job.M = 3;
+    x.job.K = x.job.ldf = n.Kp[last];
+    x.job.chunk = wp.k_last.chunk;
+    x.job.n_chunks = x.n_parts = wp.k_last.n;
+}
+
 int marf_forward(const marf_net* net, const marf_geometry* geo, const marf_c2f* c2f, const void* d_packed,
                  float* d_rgb, void* d_saved, void* stream) {
     if (!net || !d_packed || !d_rgb) return fail(MARF_ERR_INVALID, "forward: NULL argument");
@@ -873,32 +982,10 @@ int marf_backward(const marf_net* net, const marf_geometry* geo, const marf_c2f*
     }
 
     if (d_dparams) {
-        float* part = (float*)(ws + wp.part);
-        float* bpart = (float*)(ws + wp.bpart);
-        const int nl = net->n_layers;
-        for (int l = 0; l < nl - 1; ++l) {
-            {
-                MarfProfScope ps(l == 0 ? "wgrad_l0" : "wgrad_hidden", s);
-                HIPCHK(marf_launch_wgrad(wg_job(wg_shape(*net, l, a.S, wp.k), ws + wp.dz[l + 1], sv + sp.feat[l], part, bpart), s),
-                       "backward wgrad");
-            }
-            {
-                MarfProfScope ps("wgrad_reduce", s);
-                HIPCHK(marf_launch_wgrad_reduce(part, bpart, wp.k.n, net->Mp[l], net->Kp[l], net->dims[l + 1],
-                                                net->kin[l], d_dparams + net->w_off[l], d_dparams + net->b_off[l], s),
-                       "backward wgrad reduce");
-            }
-        }
-        const int l = nl - 1;
-        {
-            MarfProfScope ps("wgrad_last", s);
-            HIPCHK(marf_launch_wgrad_last(net->kdt, a.glast, sv + sp.feat[l], a.S, net->Kp[l], net->Kp[l],
-                                          wp.k_last.chunk, wp.k_last.n, part, bpart, s),
-                   "backward wgrad last");
-        }
-        HIPCHK(marf_launch_wgrad_reduce(part, bpart, wp.k_last.n, 3, net->Kp[l], 3, net->dims[l],
-                                        d_dparams + net->w_off[l], d_dparams + net->b_off[l], s),
-               "backward wgrad last reduce");
+        WgLayer wl[MARF_MAX_LAYERS];
+        wg_unfused_layers(*net, a.S, sp, wp, sv, ws, d_dparams, false, wl);
+        rc = run_wg_layers(wl, net->n_layers, k_wg_scopes, nullptr, nullptr, 1.f, nullptr, s, "backward");
+        if (rc) return rc;
     }
     if (a.geo.mode == MARF_GEO_GRID && d_dh)
         return launch_warp_bwd(a.dH_partial, a.geo.Np_pad / net->TP, a.geo, d_h_params, d_dh, lie_batch, s, nullptr,
@@ -1432,12 +1519,6 @@ static int step2_forward(const marf_net* net, const marf_geometry* geo, const ma
     return MARF_OK;
 }
 
-// record layer l's "gradient final" event, if the caller passed one
-static int mark_layer(const void* const* ev, int l, hipStream_t s) {
-    if (ev && ev[l]) HIPCHK(hipEventRecord((hipEvent_t)ev[l], s), "step_backward: layer event");
-    return MARF_OK;
-}
-
 static int step2_backward(const marf_net* net, const StepBufs& bufs, const void* d_saved, const float* d_h_params,
                           int lie_batch, const float* d_gout, const float* d_loss_out, float* d_dparams, float* d_dh,
                           hipStream_t s, const void* const* ev) {
@@ -1446,129 +1527,71 @@ static int step2_backward(const marf_net* net, const StepBufs& bufs, const void*
     const Step2BufPlan& p = bufs.p2;
     int rc;
     const char* sv = (const char*)d_saved;
-    float* part = (float*)(sv + p.part);
-    float* bpart = (float*)(sv + p.bpart);
     const float* denom = d_loss_out + 1;
     const int nl = net->n_layers;
     // (fp16x2: the saved tensors carry the dgrad's 2^10 gradient scale)
     const float post = q.variant == 3 ? 1.0f / 1024.0f : 1.0f;
+    // The list, built once, in the order the layers finish: the last layer's reduction of the step
+    // kernel's per-block partials, then layers n-2 .. 0 from what the step kernel saved -- with the
+    // pipeline on their reductions alone, the partials were computed beside the step kernel
+    // (wgrad_piece).  partl / bpartl: every layer's own partials where the plan reserved them (the
+    // fused launch, the pipeline), else the one buffer the per-layer launches share.
+    WgLayer wl[MARF_MAX_LAYERS];
+    if (d_dparams) {
+        const bool f0 = l0_recompute(net, g, p.S);
+        wg_layers(*net, d_dparams, true, wl);
+        wg_step_last(wl[0], sv + p.wlast, sv + p.blast, p.nblk, q.Kl, (float*)(sv + p.part));
+        for (int i = 1; i < nl; ++i) {
+            WgLayer& x = wl[i];
+            x.job = step2_wg_job(net, g, p, sv, x.l, p.k, (float*)(sv + p.partl[x.l]), (float*)(sv + p.bpartl[x.l]), f0);
+            x.n_parts = p.k.n;  // (pipeline off: the split the plan sized the partials by)
+            if (p.pipe.on) {
+                x.job.dz = nullptr;
+                x.n_parts = p.pipe.n_parts;
+            }
+            if (x.l == 0) x.kmap = (const int*)(sv + p.kmap);
+        }
+    }
     // The fused weight gradients (marf_launch_wgrad_fused): the hidden layers in one launch, layer 0
     // beside it on the side stream, every reduction in one launch -- the same partials and sums as
-    // the per-layer launches below (bit-identical).  The layer events follow it, in the per-layer order.
-    const int n_chunks = p.k.n;  // (pipeline off: the split the plan sized part / bpart by)
-    if (d_dparams && !p.pipe.on && p.fused_res) {
-        const int* kmap = (const int*)(sv + p.kmap);
-        const bool f0 = l0_recompute(net, g, p.S);
-        WgFusedLayer Lf[MARF_MAX_LAYERS];
-        memset(Lf, 0, sizeof(Lf));
-        int nf = 0;
-        {
-            const int l = nl - 1;  // the last layer: the step kernel's per-block partials
-            WgFusedLayer& x = Lf[nf++];  // (no product: a reduction only)
-            x.job.partial = (float*)(sv + p.wlast);
-            x.job.bpartial = (float*)(sv + p.blast);
-            x.n_parts = p.nblk;
-            x.job.M = 3;
-            x.job.K = q.Kl;
-            x.Mo = 3;
-            x.Ko = net->dims[l];
-            x.dW = d_dparams + net->w_off[l];
-            x.db = d_dparams + net->b_off[l];
-        }
-        for (int l = nl - 2; l >= 0; --l) {
-            WgFusedLayer& x = Lf[nf++];
-            x.job = step2_wg_job(net, g, p, sv, l, p.k, (float*)(sv + p.partl[l]), (float*)(sv + p.bpartl[l]), f0);
-            x.n_parts = n_chunks;
-            x.Mo = net->dims[l + 1];
-            x.Ko = net->dims[l];
-            x.dW = d_dparams + net->w_off[l];
-            x.db = d_dparams + net->b_off[l];
-            x.kmap = l == 0 ? kmap : nullptr;
-        }
-        if (marf_wgrad_fused_ok(Lf, nf)) {
-            PipeStreams* st = nullptr;
-            rc = pipe_streams(&st);
-            if (rc) return rc;
-            {
-                std::lock_guard<std::mutex> hold(st->use);
-                const char* dse = getenv("MARF_DH_SIDE");  // A/B switch (per launch): 0 = after the reductions on s
-                float* dh_side = (dse && dse[0] == '0') ? nullptr : d_dh;
-                if (dh_side) {  // s2 joins the step here (the fused launch forks it again for layer 0)
-                    HIPCHK(hipEventRecord(st->ev[2], s), "step_backward: fork");
-                    HIPCHK(hipStreamWaitEvent(st->s2, st->ev[2], 0), "step_backward: fork");
-                }
-                {
-                    MarfProfScope ps("wgrad_fused", s);
-                    HIPCHK(marf_launch_wgrad_fused(Lf, nf, d_gout, denom, s, st->s2, st->ev[0], st->ev[1], post),
-                           "step_backward fused weight gradients");
-                }
-                if (dh_side) {
-                    // the warp gradient (one block: the dH partials' fixed-order sum + the Lie
-                    // backward) reads only the step kernel's partials and the upstream gradient: it
-                    // follows layer 0 on the side stream (ahead of it, it would hold layer 0 back
-                    // until the hidden layers free a CU) and runs beside the reductions
-                    rc = launch_warp_bwd((const float*)(sv + bufs.dH), bufs.dH_per_patch, g, d_h_params, dh_side, lie_batch,
-                                         st->s2, d_gout, denom, "warp_bwd_side", "step_backward warp");
-                    if (rc) return rc;
-                    HIPCHK(hipEventRecord(st->ev[3], st->s2), "step_backward: join");
-                }
-                for (int l = nl - 1; l >= 0; --l) {  // (ahead of the warp gradient's join: the
-                    rc = mark_layer(ev, l, s);        //  layers' all-reduces do not wait for it)
-                    if (rc) return rc;
-                }
-                if (dh_side) {
-                    HIPCHK(hipStreamWaitEvent(s, st->ev[3], 0), "step_backward: join");
-                    d_dh = nullptr;
-                }
-            }
-            d_dparams = nullptr;  // done
-        }
-    }
-    // the layers finish in reverse order (last layer first, layer 0 last), each marked by its event,
-    // so that a bucketed all-reduce of finished layers overlaps the remaining weight gradients
-    if (d_dparams) {
-        const int l = nl - 1;
-        MarfProfScope ps("wgrad_last_reduce", s);
-        HIPCHK(marf_launch_wgrad_reduce((const float*)(sv + p.wlast), (const float*)(sv + p.blast), p.nblk, 3, q.Kl, 3,
-                                        net->dims[l], d_dparams + net->w_off[l], d_dparams + net->b_off[l], s, d_gout,
-                                        denom, part),
-               "step_backward last reduce");
-        rc = mark_layer(ev, l, s);
+    // the per-layer launches (bit-identical).  The layer events follow it, in the per-layer order.
+    if (d_dparams && !p.pipe.on && p.fused_res && marf_wgrad_fused_ok(wl, nl)) {
+        PipeStreams* st = nullptr;
+        rc = pipe_streams(&st);
         if (rc) return rc;
-    }
-    if (d_dparams && p.pipe.on) {  // the split-K partials were computed beside the step kernel
-        const int* kmap = (const int*)(sv + p.kmap);
-        for (int l = nl - 2; l >= 0; --l) {
-            const int K = l == 0 ? q.ldf0 : net->Kp[l];
-            MarfProfScope ps("wgrad_reduce", s);
-            HIPCHK(marf_launch_wgrad_reduce((const float*)(sv + p.partl[l]), (const float*)(sv + p.bpartl[l]),
-                                            p.pipe.n_parts, net->Mp[l], K, net->dims[l + 1], net->dims[l],
-                                            d_dparams + net->w_off[l], d_dparams + net->b_off[l], s, d_gout, denom,
-                                            nullptr, l == 0 ? kmap : nullptr),
-                   "step_backward wgrad reduce (pipelined)");
-            rc = mark_layer(ev, l, s);
+        std::lock_guard<std::mutex> hold(st->use);
+        const char* dse = getenv("MARF_DH_SIDE");  // A/B switch (per launch): 0 = after the reductions on s
+        float* dh_side = (dse && dse[0] == '0') ? nullptr : d_dh;
+        if (dh_side) {  // s2 joins the step here (the fused launch forks it again for layer 0)
+            HIPCHK(hipEventRecord(st->ev[2], s), "step_backward: fork");
+            HIPCHK(hipStreamWaitEvent(st->s2, st->ev[2], 0), "step_backward: fork");
+        }
+        {
+            MarfProfScope ps("wgrad_fused", s);
+            HIPCHK(marf_launch_wgrad_fused(wl, nl, d_gout, denom, s, st->s2, st->ev[0], st->ev[1], post),
+                   "step_backward fused weight gradients");
+        }
+        if (dh_side) {
+            // the warp gradient (one block: the dH partials' fixed-order sum + the Lie backward) reads
+            // only the step kernel's partials and the upstream gradient: it follows layer 0 on the side
+            // stream (ahead of it, it would hold layer 0 back until the hidden layers free a CU) and
+            // runs beside the reductions
+            rc = launch_warp_bwd((const float*)(sv + bufs.dH), bufs.dH_per_patch, g, d_h_params, dh_side, lie_batch,
+                                 st->s2, d_gout, denom, "warp_bwd_side", "step_backward warp");
             if (rc) return rc;
+            HIPCHK(hipEventRecord(st->ev[3], st->s2), "step_backward: join");
+        }
+        for (int l = nl - 1; l >= 0; --l) {  // (ahead of the warp gradient's join: the layers'
+            rc = mark_layer(ev, l, s);        //  all-reduces do not wait for it)
+            if (rc) return rc;
+        }
+        if (dh_side) {
+            HIPCHK(hipStreamWaitEvent(s, st->ev[3], 0), "step_backward: join");
+            d_dh = nullptr;
         }
     } else if (d_dparams) {
-        const int* kmap = (const int*)(sv + p.kmap);
-        const bool f0 = l0_recompute(net, g, p.S);
-        for (int l = nl - 2; l >= 0; --l) {
-            const int K = l == 0 ? q.ldf0 : net->Kp[l];
-            {
-                MarfProfScope ps(l == 0 ? "wgrad_l0" : "wgrad_hidden", s);
-                HIPCHK(marf_launch_wgrad(step2_wg_job(net, g, p, sv, l, p.k, part, bpart, f0), s),
-                       l == 0 && f0 ? "step_backward wgrad_l0 (feat_0 recomputed)" : "step_backward wgrad");
-            }
-            {
-                MarfProfScope ps("wgrad_reduce", s);
-                HIPCHK(marf_launch_wgrad_reduce(part, bpart, n_chunks, net->Mp[l], K, net->dims[l + 1], net->dims[l],
-                                                d_dparams + net->w_off[l], d_dparams + net->b_off[l], s, d_gout, denom,
-                                                nullptr, l == 0 ? kmap : nullptr, post),
-                       "step_backward wgrad reduce");
-            }
-            rc = mark_layer(ev, l, s);
-            if (rc) return rc;
-        }
+        rc = run_wg_layers(wl, nl, k_wg_step_scopes, d_gout, denom, post, ev, s, "step_backward");
+        if (rc) return rc;
     }
     if (d_dh)
         return launch_warp_bwd((const float*)(sv + bufs.dH), bufs.dH_per_patch, g, d_h_params, d_dh, lie_batch, s, d_gout,
@@ -1670,6 +1693,37 @@ static int tile_step_forward(const marf_net* net, const marf_geometry* geo, cons
     return MARF_OK;
 }
 
+// The tile kernels' step backward: the last layer's reduction of the per-tile partials, then layers
+// n-2 .. 0 from the saved feat_l / dz_{l+1} through one partial buffer, then the warp gradient.
+static int tile_step_backward(const marf_net* net, const StepBufs& bufs, const void* d_saved, const float* d_h_params,
+                              int lie_batch, const float* d_gout, const float* d_loss_out, float* d_dparams, float* d_dh,
+                              hipStream_t s, const void* const* ev) {
+    const GeoDev& g = bufs.g;
+    const StepPlan& p = bufs.pt;
+    const long long S = (long long)g.B * g.Np_pad;
+    const char* sv = (const char*)d_saved;
+    float* part = (float*)(sv + p.part);
+    float* bpart = (float*)(sv + p.bpart);
+    const float* denom = d_loss_out + 1;
+    const int nl = net->n_layers;
+    if (d_dparams) {
+        WgLayer wl[MARF_MAX_LAYERS];
+        wg_layers(*net, d_dparams, true, wl);
+        wg_step_last(wl[0], sv + p.wlast, sv + p.blast, p.n_tiles, net->Kp[nl - 1], part);
+        for (int i = 1; i < nl; ++i) {
+            const int l = wl[i].l;
+            wl[i].job = wg_job(wg_shape(*net, l, S, p.k), sv + p.dz[l + 1], sv + p.feat[l], part, bpart);
+            wl[i].n_parts = p.k.n;
+        }
+        const int rc = run_wg_layers(wl, nl, k_wg_step_scopes, d_gout, denom, 1.f, ev, s, "step_backward");
+        if (rc) return rc;
+    }
+    if (d_dh)
+        return launch_warp_bwd((const float*)(sv + bufs.dH), bufs.dH_per_patch, g, d_h_params, d_dh, lie_batch, s, d_gout,
+                               denom, "warp_bwd", "step_backward warp");
+    return MARF_OK;
+}
+
 int marf_step_forward(const marf_net* net, const marf_geometry* geo, const marf_c2f* c2f, const void* d_packed,
                       const float* d_gt, const float* d_mask, const float* d_denom_override, float* d_rgb,
                       float* d_loss_out, void* d_saved, void* stream) {
@@ -1701,46 +1755,7 @@ int marf_step_backward_ev(const marf_net* net, const marf_geometry* geo, const v
     if (rc) return rc;
     if (use_step2(net))
         return step2_backward(net, bufs, d_saved, d_h_params, lie_batch, d_gout, d_loss_out, d_dparams, d_dh, s, ev);
-    const GeoDev& g = bufs.g;
-    const StepPlan& p = bufs.pt;
-    const long long S = (long long)g.B * g.Np_pad;
-    const char* sv = (const char*)d_saved;
-    float* part = (float*)(sv + p.part);
-    float* bpart = (float*)(sv + p.bpart);
-    const float* denom = d_loss_out + 1;
-    const int nl = net->n_layers;
-    if (d_dparams) {  // last layer first, then l = nl-2 .. 0, each marked by its event (as step2_backward)
-        {
-            const int l = nl - 1;
-            MarfProfScope ps("wgrad_last_reduce", s);
-            HIPCHK(marf_launch_wgrad_reduce((const float*)(sv + p.wlast), (const float*)(sv + p.blast), p.n_tiles, 3,
-                                            net->Kp[l], 3, net->dims[l], d_dparams + net->w_off[l],
-                                            d_dparams + net->b_off[l], s, d_gout, denom, part),
-                   "step_backward last reduce");
-            rc = mark_layer(ev, l, s);
-            if (rc) return rc;
-        }
-        for (int l = nl - 2; l >= 0; --l) {
-            {
-                MarfProfScope ps(l == 0 ? "wgrad_l0" : "wgrad_hidden", s);
-                HIPCHK(marf_launch_wgrad(wg_job(wg_shape(*net, l, S, p.k), sv + p.dz[l + 1], sv + p.feat[l], part, bpart), s),
-                       "step_backward wgrad");
-            }
-            {
-                MarfProfScope ps("wgrad_reduce", s);
-                HIPCHK(marf_launch_wgrad_reduce(part, bpart, p.k.n, net->Mp[l], net->Kp[l], net->dims[l + 1],
-                                                net->kin[l], d_dparams + net->w_off[l], d_dparams + net->b_off[l], s,
-                                                d_gout, denom),
-                       "step_backward wgrad reduce");
-            }
-            rc = mark_layer(ev, l, s);
-            if (rc) return rc;
-        }
-    }
-    if (d_dh)
-        return launch_warp_bwd((const float*)(sv + bufs.dH), bufs.dH_per_patch, g, d_h_params, d_dh, lie_batch, s, d_gout,
-                               denom, "warp_bwd", "step_backward warp");
-    return MARF_OK;
+    return tile_step_backward(net, bufs, d_saved, d_h_params, lie_batch, d_gout, d_loss_out, d_dparams, d_dh, s, ev);
 }
 
 // ---- the warp-only step: a frozen image registers further patches (include/marf.h)
@@ -1988,38 +2003,9 @@ int marf_mask_backward(const marf_mask_net* net, const marf_geometry* geo, const
         HIPCHK(marf_launch_mask_bwd(a, net->lds, (int)(S / net->TP), s), "mask_backward dgrad");
     }
     // weight / bias gradients: the generic split-K launchers and their fixed-order reductions
-    float* part = (float*)(ws + wp.part);
-    float* bpart = (float*)(ws + wp.bpart);
-    const int nl = net->n_layers;
-    for (int l = 0; l < nl - 1; ++l) {
-        {
-            MarfProfScope ps(l == 0 ? "mask_wgrad_l0" : "mask_wgrad_hidden", s);
-            WgJob w = wg_job(wg_shape(*net, l, S, wp.k), ws + wp.dz[l + 1], sv + sp.feat[l], part, bpart);
-            if (net->split) {  // hi plane [S][Kp], the lo plane behind it
-                w.split = true;
-                w.dz_lo = (const char*)w.dz + (size_t)S * net->Kp[l + 1] * 2;
-                w.feat_lo = (const char*)w.feat + (size_t)S * net->Kp[l] * 2;
-            }
-            HIPCHK(marf_launch_wgrad(w, s), "mask_backward wgrad");
-        }
-        MarfProfScope ps("mask_wgrad_reduce", s);
-        HIPCHK(marf_launch_wgrad_reduce(part, bpart, wp.k.n, net->Mp[l], net->Kp[l], net->dims[l + 1],
-                                        net->dims[l], d_dparams + net->w_off[l], d_dparams + net->b_off[l], s),
-               "mask_backward wgrad reduce");
-    }
-    const int l = nl - 1;
-    {
-        MarfProfScope ps("mask_wgrad_last", s);
-        // (split: feat_{n-1} was saved as fp32, float(hi) + float(lo): the fp32 kernel serves both recipes)
-        HIPCHK(marf_launch_wgrad_last(0, a.glast, sv + sp.feat[l], S, net->Kp[l], net->Kp[l], wp.k_last.chunk,
-                                      wp.k_last.n, part, bpart, s),
-               "mask_backward wgrad last");
-    }
-    // glast rows 1..3 are zero: row 0 of the 3-row partial is the one real output row
-    HIPCHK(marf_launch_wgrad_reduce(part, bpart, wp.k_last.n, 3, net->Kp[l], 1, net->dims[l],
-                                    d_dparams + net->w_off[l], d_dparams + net->b_off[l], s),
-           "mask_backward wgrad last reduce");
-    return MARF_OK;
+    WgLayer wl[MARF_MAX_LAYERS];
+    wg_unfused_layers(*net, S, sp, wp, sv, ws, d_dparams, net->split != 0, wl);
+    return run_wg_layers(wl, net->n_layers, k_mask_wg_scopes, nullptr, nullptr, 1.f, nullptr, s, "mask_backward");
 }
 
 int marf_edge_map(const float* d_img, int n_img, int H, int W, double* d_out, void* stream) {

@@ -329,23 +329,27 @@ static_assert(is(stride(hidden(), 260), true, WG_STAGED, 256, 256), "a feat stri
 // MARF_WGRAD_DMA (A/B switch, read here at every call: 0 = register-staged kernels) into wg_pick
 WgPick marf_wgrad_pick(const WgShape& w);
 hipError_t marf_launch_wgrad(const WgJob& j, hipStream_t s);
-// One layer of the fused weight-gradient launch (marf_launch_wgrad_fused): its product (job.dz null:
-// none, the partials are there already) and the fixed-order reduction of n_parts partials into dW
-// [Mo][Ko] / db [Mo]
-struct WgFusedLayer {
+// One layer's weight gradient, as every backward lists it: its product (job.dz and glast null: none,
+// the partials [n_parts][job.M][job.K] are there already) and the fixed-order reduction of n_parts
+// partials into dW [Mo][Ko] / db [Mo]
+struct WgLayer {
     WgJob job;
-    int n_parts;      // partials to reduce (with a product: its n_chunks)
+    const float* glast;  // the unfused last layer's product (marf_launch_wgrad_last): glast (x) job.feat over
+                         // job.S rows split by job.chunk / n_chunks into job.partial [n_chunks][3][job.K]
+    int l;               // the layer (its event, its profile scope)
+    int n_parts;         // partials to reduce (with a product: its n_chunks)
     int Mo, Ko;
     float* dW;
     float* db;
-    const int* kmap;  // layer 0: column of true input feature k in the partial
+    const int* kmap;     // layer 0: column of true input feature k in the partial
+    float* scratch;      // where a reduction above 1,024 partials folds them first (null: it never has as many)
 };
-// every layer on a one-block LDS-DMA 256 kernel (the hidden layers) in one launch on s, the one
-// other product (layer 0) beside it on s2 (fork / join events), then every layer's reduction in one
-// launch on s; false if a shape does not qualify.  post: the exact power of two the products'
-// partials carry the inverse of (2^-10: the fp16x2 recipe)
-bool marf_wgrad_fused_ok(const WgFusedLayer* layers, int n_layers);
-hipError_t marf_launch_wgrad_fused(const WgFusedLayer* layers, int n_layers, const float* gscale, const float* denom,
+// The fused launch of a list: every layer on a one-block LDS-DMA 256 kernel (the hidden layers) in
+// one launch on s, the one other product (layer 0) beside it on s2 (fork / join events), then every
+// layer's reduction in one launch on s; false if a shape does not qualify.  post: the exact power of
+// two the products' partials carry the inverse of (2^-10: the fp16x2 recipe)
+bool marf_wgrad_fused_ok(const WgLayer* layers, int n_layers);
+hipError_t marf_launch_wgrad_fused(const WgLayer* layers, int n_layers, const float* gscale, const float* denom,
                                    hipStream_t s, hipStream_t s2, hipEvent_t fork, hipEvent_t join, float post = 1.f);
 hipError_t marf_launch_wgrad_last(int dtype, const float* glast, const void* feat, long long S, int ldf, int K,
                                   int chunk, int n_chunks, float* partial, float* bpartial, hipStream_t s);

@@ -1005,7 +1005,7 @@ static bool wg_in_layers(const WgJob& j, const WgPick& pk) {
     return (pk.k == WG_DMA256 || pk.k == WG_DMA_DZL) && j.t16 && pk.blocks(j) == 1;
 }
 
-bool marf_wgrad_fused_ok(const WgFusedLayer* layers, int n_layers) {
+bool marf_wgrad_fused_ok(const WgLayer* layers, int n_layers) {
     if (!layers || n_layers < 1 || n_layers > WF_MAXJ) return false;
     if (const char* e = getenv("MARF_WGRAD_FUSED")) {  // A/B switch (read per launch): 0 = per-layer launches
         if (e[0] == '0') return false;
@@ -1015,9 +1015,9 @@ bool marf_wgrad_fused_ok(const WgFusedLayer* layers, int n_layers) {
     const WgJob* first = nullptr;  // the products share one split of the pixel rows
     int n_side = 0;
     for (int i = 0; i < n_layers; ++i) {
-        const WgFusedLayer& L = layers[i];
+        const WgLayer& L = layers[i];
         const WgJob& j = L.job;
-        if (L.Mo > j.M || L.Ko > j.K || !j.partial || !j.bpartial || !L.dW || !L.db) return false;
+        if (L.glast || L.Mo > j.M || L.Ko > j.K || !j.partial || !j.bpartial || !L.dW || !L.db) return false;
         if (!j.dz) {  // reduction only
             if (L.n_parts < 1 || L.n_parts > 1024) return false;  // (the per-layer path folds above 1024)
             continue;
@@ -1033,7 +1033,7 @@ bool marf_wgrad_fused_ok(const WgFusedLayer* layers, int n_layers) {
     return n_side <= 1;
 }
 
-hipError_t marf_launch_wgrad_fused(const WgFusedLayer* layers, int n_layers, const float* gscale, const float* denom,
+hipError_t marf_launch_wgrad_fused(const WgLayer* layers, int n_layers, const float* gscale, const float* denom,
                                    hipStream_t s, hipStream_t s2, hipEvent_t fork, hipEvent_t join, float post) {
     hipError_t e;
     // every hidden layer's chunks: one launch, layer-major blocks; layer 0 on s2, beside them
@@ -1089,7 +1089,7 @@ hipError_t marf_launch_wgrad_fused(const WgFusedLayer* layers, int n_layers, con
     r.denom = denom;
     int blk = 0;
     for (int i = 0; i < n_layers; ++i) {
-        const WgFusedLayer& Ly = layers[i];
+        const WgLayer& Ly = layers[i];
         // (a reduction-only layer, the last: its partials are unscaled in the step kernel)
         r.job[i] = {Ly.job.partial, Ly.job.bpartial, Ly.n_parts, Ly.job.M, Ly.job.K, Ly.Mo, Ly.Ko, blk, Ly.dW, Ly.db, Ly.kmap,
                     Ly.job.dz ? post : 1.f};

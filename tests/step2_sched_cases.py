@@ -22,6 +22,12 @@ paths that no case above does: the per-layer launches of the LDS-DMA kernel with
 recomputing instantiations, the register-staged kernel on T16 tensors, range mode (the pipelined
 step), more than one output block per chunk under both block maps, and fp32 fragments in 128 x 64
 blocks.  Same rule (the parent library, three separate processes); none had to be left out.
+
+wg-fold ("backward_layer_cases" in the fixture, with its parent commit) pins the last-layer
+reduction of a step above 1,024 partials, which folds them first.  Same rule; kept.
+
+`case_launches` counts a case's launches per profile scope (tests/golden/backward_launches.json,
+test_gpu_backward_launches.py).
 """
 import hashlib
 import os
@@ -94,6 +100,11 @@ CASES = {
     "wg-wide-bf16-x8": (1, 64, 64, 8, [512, 512], {}, {"precision": "bf16"}),
     # fp32 fragments in 128 x 64 output blocks (M = 128 and M = 96)
     "wg-fp32-narrow": (1, 64, 64, 8, [128, 96, 128], {}, {"precision": "fp32"}),
+    # ---- "backward_layer_cases" in the fixture
+    # the last-layer reduction above 1,024 partials: k_fold_partials into the step buffer's `part`, then
+    # the reduction of its groups.  fp32 tiles hold 64 slots; 13,456 pixels per patch pad to 13,568
+    # slots = 212 tiles (the 211th holds 16 pixels, the 212th none), 5 patches: 1,060 tiles
+    "wg-fold": (5, 116, 116, 8, [128, 96, 128], {}, {"precision": "fp32"}),
 }
 # the FWD instantiation of k_mlp_step_split: Model.predict_entire_image of the 6 x 128 net on a
 # 45 x 61 canvas (2,745 pixels: no multiple of 128)
@@ -102,6 +113,11 @@ RENDER_CASES = {"render-deep": (45, 61, 8, [128] * 6)}
 # cases of mask_split_ref.py: m and every parameter gradient of marf_hip.mask_forward + backward
 MASK_CASES = {f"mask-{prec}-{shape}": (prec, shape) for prec in ("fp32", "bf16x3a") for shape in ("ragged", "tiny", "exact")}
 ALL_CASES = list(CASES) + list(RENDER_CASES) + list(MASK_CASES)
+# the launch census (case_launches): the fused weight gradients (plain and with `post`), the per-layer
+# launches on recomputed and on stored operands, the pipelined step, the tile step in bf16 and fp32, the
+# split tile step, the separate forward / backward path and the mask network in both recipes
+LAUNCH_CASES = ["acc", "fp16x2", "wg-perlayer", "wg-stored", "wg-ranged", "tile-bf16", "tile-fp32", "split-tp128",
+                "plain-fwd-bwd", "mask-fp32-tiny", "mask-bf16x3a-tiny"]
 
 
 def build(case, setenv, out="/tmp/marf_sched"):
@@ -188,6 +204,26 @@ def mask_bits(case):
     out.update({name: p.grad for name, p in zip(MASK_PARAM_NAMES, ps)})
     assert all(torch.isfinite(v).all() for v in out.values()), case
     return {"kernel": "k_mask_fwd+k_mask_bwd " + prec, "bits": {k: digest(v) for k, v in out.items()}}
+
+
+def case_launches(case, setenv):
+    """{profile scope: launches} of one step of `case` (the mask network's forward + backward), counted
+    by the library's profile hooks; profiling is off again and reset afterwards."""
+    import marf_hip
+    marf_hip.profile_enable(True)
+    try:
+        if case in MASK_CASES:
+            marf_hip.profile_reset()
+            mask_bits(case)
+        else:
+            m, var = build(case, setenv)
+            marf_hip.profile_reset()
+            step(m, var)
+        torch.cuda.synchronize()
+        return {name: int(n) for name, (_, n) in marf_hip.profile_read().items()}
+    finally:
+        marf_hip.profile_enable(False)
+        marf_hip.profile_reset()
 
 
 def case_bits(case, setenv):
