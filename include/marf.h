@@ -236,6 +236,33 @@ int marf_warp_step_forward(const marf_net* net, const marf_geometry* geo, const 
 int marf_warp_step_backward(const marf_net* net, const marf_geometry* geo, const void* d_saved, const float* d_h_params,
                             int lie_batch, const float* d_gout, const float* d_loss_out, float* d_dh, void* stream);
 
+/* ---- Gauss-Newton normal equations of the registration problem on a frozen image (an extension: the
+ * reference walks the warps downhill with Adam, model/planar.py:98-99).  With the image frozen the B
+ * patches are independent 8-parameter non-linear least-squares problems.  Per patch b and real pixel q,
+ * with p the sigmoid output, g the target, m the mask:
+ *     r_qc = m_q (p_qc - g_qc)        J_qc = m_q d p_qc / d vec(H_b)   (a row of 9, H_b row-major)
+ * marf_gn_normal writes d_out[b] = [sse = sum r^2, msum = sum m, g9 = sum_qc J_qc^T r_qc (9), N = sum_qc
+ * J_qc^T J_qc (9 x 9 symmetric: the upper triangle, row-major, 45 values)] in fp64, and rgb [B][Np][3]
+ * (may be NULL); with loss_only the forward alone runs and only sse and msum are written, with the full
+ * launch's bits.  One tile kernel carries the three channel gradients down the dgrad chain and sums a
+ * 56-value partial per tile, a second sums a patch's partials, both in a fixed order without atomics:
+ * two calls on the same inputs give the same bits.  The chain to the tangent (d vec(H) / d h from
+ * marf_sl3_to_SL3_backward) and the solver are the caller's (marf_hip.gn_normal, model/planar.py).
+ * The image's weights are packed once into a buffer of the feature's own (marf_gn_packed_bytes /
+ * marf_gn_pack): the fp32 tile layouts, or for a MARF_BF16X3 net -- one in k_step2's reach included --
+ * the tile layouts with every image as hi then lo; the arithmetic is exact fp32 MFMA, or the split tile
+ * recipe's three terms in the forward and the dgrad.  d_scratch (marf_gn_scratch_bytes) holds the
+ * ReLU records, the tile partials and the band weights.  MARF_ERR_UNSUPPORTED with the reason (the
+ * byte counts: 0 and the reason in marf_last_error) for MARF_BF16, MARF_FP16 and MARF_FP16X2 nets (a
+ * 16-bit Jacobian misses the warp gradient's bound), skip nets, MARF_GEO_COORDS, and a shape whose
+ * tile does not fit LDS (marf_gn_scratch_bytes / marf_gn_normal). */
+size_t marf_gn_packed_bytes(const marf_net* net);
+int marf_gn_pack(const marf_net* net, const float* d_params, void* d_gn_packed, void* stream);
+size_t marf_gn_scratch_bytes(const marf_net* net, const marf_geometry* geo);
+int marf_gn_normal(const marf_net* net, const marf_geometry* geo, const marf_c2f* c2f, const void* d_gn_packed,
+                   const float* d_gt, const float* d_mask, int loss_only, float* d_rgb, double* d_out, void* d_scratch,
+                   void* stream);
+
 /* ---- MLP-gradient exchange of the patch-sharded step (the reference is
  * single-GPU, options.py:117-120, so this replaces no reference call: it is the one collective the
  * sharding adds).  RCCL over xGMI, librccl.so opened at first use.  marf_comm_unique_id fills 128

@@ -1797,6 +1797,141 @@ int marf_warp_step_backward(const marf_net* net, const marf_geometry* geo, const
                            (hipStream_t)stream, d_gout, d_loss_out + 1, "warp_bwd", "warp_step_backward warp");
 }
 
+// ---- Gauss-Newton normal equations on a frozen image (include/marf.h; marf_gn.hip)
+
+// why a net has no Gauss-Newton kernel (null: it has one)
+static const char* gn_refusal(const marf_net* n) {
+    if (n->dtype == MARF_BF16 || n->dtype == MARF_FP16 || n->dtype == MARF_FP16X2)
+        return "a 16-bit Jacobian (bf16, fp16, fp16x2) misses the warp gradient's bound; use fp32 or bf16x3";
+    if (n->skip) return "skip nets have no Gauss-Newton kernel";
+    return nullptr;
+}
+
+// The feature's own net plan: the tile layouts of every net it takes -- fp32, or every image hi then
+// lo for a MARF_BF16X3 net, those of k_step2's reach included (their training buffer holds only the
+// weight program) -- in a packed buffer of its own, and its tile: bf16x3 TP = 128 up to 256 wide, 64
+// above (k_mlp_step_split's), fp32 TP = 64.
+struct GnNet {
+    NetShape s;
+    bool split;
+    int TP, lda;
+    size_t lds, lds_static;
+};
+static void plan_gn_net(const marf_net* n, GnNet& q) {
+    q.s = *n;
+    q.split = n->dtype == MARF_BF16X3;
+    q.s.kdt = q.split ? 1 : 0;
+    q.s.elem = q.split ? 2 : 4;
+    plan_params(q.s, 4);  // fp32 weights, or a bf16 hi and a bf16 lo image
+    q.TP = q.split ? (n->Kmax > 256 ? 64 : 128) : 64;
+    q.lda = q.split ? n->Kmax + 8 : n->Kmax + 1;
+    const size_t tile = q.split ? (size_t)2 * q.TP * q.lda * 2 : (size_t)q.TP * q.lda * 4;
+    q.lds = std::max(tile, (size_t)q.TP * (n->Kp[0] + 1) * 4);
+    // k_gn's static __shared__: wsh, red, gl, lsum, rs, the three (du, dv) images, the per-slot
+    // products of the reduction (+ alignment slack)
+    q.lds_static = 128 + 64 * 4 * 2 * 4 + (size_t)q.TP * (16 + 2 * 4 + 32 + 3 * 2 * 4 + 12 * 4) + 512;
+    q.s.TP = q.TP;
+    q.s.lda = q.lda;
+}
+
+// the scratch of a launch: the ReLU records the kernel's own dgrad passes re-read, one 56-value fp64
+// partial per tile, the band weights
+struct GnPlan {
+    size_t mask[MARF_MAX_LAYERS], part, c2f, total;
+    int n_tiles;
+};
+static void plan_gn(const GnNet& q, long long S, GnPlan& p) {
+    memset(&p, 0, sizeof(p));
+    Layout at;
+    p.n_tiles = (int)(S / q.TP);
+    for (int l = 1; l < q.s.n_layers; ++l) p.mask[l] = at.take((long long)p.n_tiles * 4 * 1024);
+    p.part = at.take((long long)p.n_tiles * 56 * 8);
+    p.c2f = at.take(256);
+    p.total = at.off;
+}
+
+size_t marf_gn_packed_bytes(const marf_net* net) {
+    if (!net) return 0;
+    if (const char* why = gn_refusal(net)) {
+        fail(MARF_ERR_UNSUPPORTED, "gn: %s", why);
+        return 0;
+    }
+    GnNet q;
+    plan_gn_net(net, q);
+    return q.s.packed_bytes;
+}
+
+int marf_gn_pack(const marf_net* net, const float* d_params, void* d_gn_packed, void* stream) {
+    if (!net || !d_params || !d_gn_packed) return fail(MARF_ERR_INVALID, "gn_pack: NULL argument");
+    if (const char* why = gn_refusal(net)) return fail(MARF_ERR_UNSUPPORTED, "gn_pack: %s", why);
+    GnNet q;
+    plan_gn_net(net, q);
+    PackArgs a;
+    const long long mx = fill_pack_args(q.s, a);
+    MarfProfScope ps("gn_pack", (hipStream_t)stream);
+    HIPCHK(marf_launch_pack(q.split ? 3 : 0, d_params, (char*)d_gn_packed, a, mx, (hipStream_t)stream), "gn_pack");
+    return MARF_OK;
+}
+
+// the geometry and the plans of a launch; the refusals that depend on the shape are made here
+static int plan_gn_bufs(const marf_net* net, const marf_geometry* geo, const char* who, GnNet& q, GeoDev& g, GnPlan& p) {
+    if (const char* why = gn_refusal(net)) return fail(MARF_ERR_UNSUPPORTED, "%s: %s", who, why);
+    if (!geo) return fail(MARF_ERR_INVALID, "%s: geometry is NULL", who);
+    if (geo->mode == MARF_GEO_COORDS)
+        return fail(MARF_ERR_UNSUPPORTED, "%s: COORDS geometry has no homography to solve for; needs a pixel-grid geometry", who);
+    plan_gn_net(net, q);
+    if (q.lds + q.lds_static > 160 * 1024)
+        return fail(MARF_ERR_UNSUPPORTED, "%s: tile does not fit LDS (%zu B dynamic + %zu B static)", who, q.lds, q.lds_static);
+    int rc = make_geo(geo, g, MARF_TILE_PAD);
+    if (rc) return rc;
+    plan_gn(q, (long long)g.B * g.Np_pad, p);
+    return MARF_OK;
+}
+
+size_t marf_gn_scratch_bytes(const marf_net* net, const marf_geometry* geo) {
+    if (!net) return 0;
+    GnNet q;
+    GeoDev g;
+    GnPlan p;
+    if (plan_gn_bufs(net, geo, "gn_scratch_bytes", q, g, p) != MARF_OK) return 0;
+    return p.total;
+}
+
+int marf_gn_normal(const marf_net* net, const marf_geometry* geo, const marf_c2f* c2f, const void* d_gn_packed,
+                   const float* d_gt, const float* d_mask, int loss_only, float* d_rgb, double* d_out, void* d_scratch,
+                   void* stream) {
+    if (!net || !d_gn_packed || !d_gt || !d_out || !d_scratch) return fail(MARF_ERR_INVALID, "gn_normal: NULL argument");
+    hipStream_t s = (hipStream_t)stream;
+    GnNet q;
+    GnPlan p;
+    GnArgs ga;
+    memset(&ga, 0, sizeof(ga));
+    StepArgs& a = ga.s;
+    int rc = plan_gn_bufs(net, geo, "gn_normal", q, a.geo, p);
+    if (rc) return rc;
+    fill_netdev(q.s, net->L, d_gn_packed, a.net);
+    a.c2f = make_c2f(c2f);
+    a.rgb = d_rgb;
+    a.gt = d_gt;
+    a.mask = d_mask;
+    a.S = (long long)a.geo.B * a.geo.Np_pad;
+    a.lda = q.lda;
+    char* sv = (char*)d_scratch;
+    for (int l = 1; l < net->n_layers; ++l) a.mask_bits[l] = (uint64_t*)(sv + p.mask[l]);
+    a.c2f_w = (const float*)(sv + p.c2f);
+    ga.partial = (double*)(sv + p.part);
+    if (net->L > 0) HIPCHK(marf_launch_c2f_weights(a.c2f, net->L, (float*)(sv + p.c2f), s), "gn_normal c2f");
+    {
+        MarfProfScope ps(loss_only ? "gn_loss" : "gn", s);
+        HIPCHK(marf_launch_gn(ga, q.split, q.TP, loss_only != 0, q.lds, p.n_tiles, s), "gn_normal");
+    }
+    {
+        MarfProfScope ps("gn_reduce", s);
+        HIPCHK(marf_launch_gn_reduce(ga.partial, a.geo.Np_pad / q.TP, a.geo.B, loss_only != 0, d_out, s), "gn_normal reduce");
+    }
+    return MARF_OK;
+}
+
 // ------------------------------------------------------------------ loss / optimizer
 
 size_t marf_mse_workspace_bytes(void) { return 1024 * 2 * sizeof(double); }

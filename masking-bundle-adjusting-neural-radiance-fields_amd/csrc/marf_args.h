@@ -58,6 +58,14 @@ struct StepArgs {
     int lda;
 };
 
+// Gauss-Newton normal equations on a frozen image (marf_gn.hip): the step's inputs (s: net, geo, c2f,
+// rgb, gt, mask, mask_bits, c2f_w, lda; nothing is saved, no dH / loss partials) and the per-tile
+// partials [n_tiles][56] = sse, msum, g9 (9), N upper triangle row-major (45).
+struct GnArgs {
+    StepArgs s;
+    double* partial;
+};
+
 // Implicit-mask network (marf_mask.hip; reference model/planar.py:340-349, 475-488): the per-pixel
 // input [E[r] ; E[g] ; E[b] ; uv] is built in LDS, the layers run as the tile kernels' do.
 struct MaskFwdArgs {
@@ -368,6 +376,13 @@ hipError_t marf_launch_mlp_step(const marf::StepArgs& a, int dtype, int TP, int 
 // the split tile step of MARF_BF16X3 nets beyond k_step2's reach (marf_step_split.hip); TP 64 or 128
 hipError_t marf_launch_mlp_step_split(const marf::StepArgs& a, int TP, bool fwd_only, size_t lds, int n_tiles,
                                       hipStream_t s, bool warp_only = false);
+// the Gauss-Newton tile kernel (marf_gn.hip): split = the bf16x3 tile recipe (TP 128 or 64), else fp32
+// (TP 64); loss_only: forward, sse and msum only.  Then a patch's tile partials summed in tile order
+// into out [B][56] (loss_only: the first two values).
+hipError_t marf_launch_gn(const marf::GnArgs& a, bool split, int TP, bool loss_only, size_t lds, int n_tiles,
+                          hipStream_t s);
+hipError_t marf_launch_gn_reduce(const double* partial, int tiles_per_patch, int B, bool loss_only, double* out,
+                                 hipStream_t s);
 hipError_t marf_launch_c2f_weights(const marf::C2fDev& c, int L, float* out, hipStream_t s,
                                    const int* csrc = nullptr, int* cdst = nullptr, int cn = 0);
 hipError_t marf_launch_loss_final(const double* part, int n, float* out, const float* denom_override, hipStream_t s);

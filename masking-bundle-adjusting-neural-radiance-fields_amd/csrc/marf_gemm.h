@@ -447,7 +447,10 @@ MARF_DEV int skip_lds_off(const NetDev& net, int lda) {
 // warp_adjoint_tail: everything after the layer-0 dgrad GEMM (acc = d feat_0, every wave past the
 // barrier that follows the GEMM), shared with the split tile step, which runs its own three-term
 // GEMM.  FAST: the posenc sin / cos of the 16-bit prologue (band_sincos).
-template <class P, int TP, bool GRID_ONLY, int NW, bool FAST, int RT, int PT>
+// UV_ONLY: the tail stops at the per-slot (du, dv), written for every slot of the tile to
+// d_coords[2 slot] (a tile-local [TP][2] image, LDS or global; no barrier behind it) -- the
+// Gauss-Newton kernel (marf_gn.hip), which runs the tail once per output channel; no dH, red9 unused.
+template <class P, int TP, bool GRID_ONLY, int NW, bool FAST, int RT, int PT, bool UV_ONLY = false>
 MARF_DEV void warp_adjoint_tail(const f32x16 (&acc)[RT][PT], const NetDev& net, const GeoDev& geo, int c2f_on,
                                 const float* wsh, char* smem, int wave, int lane, int b, int p0, float* red,
                                 float* red9, float* dH_partial, float* d_coords, unsigned long long* sp,
@@ -516,7 +519,10 @@ MARF_DEV void warp_adjoint_tail(const f32x16 (&acc)[RT][PT], const NetDev& net, 
             du += red[(q * TP + i) * 2];
             dv += red[(q * TP + i) * 2 + 1];
         }
-        if (geo.mode == 1) {
+        if constexpr (UV_ONLY) {
+            d_coords[2 * i] = du;
+            d_coords[2 * i + 1] = dv;
+        } else if (geo.mode == 1) {
             if (valid && d_coords) {
                 d_coords[2 * (size_t)(p0 + i)] = du;
                 d_coords[2 * (size_t)(p0 + i) + 1] = dv;
@@ -536,6 +542,7 @@ MARF_DEV void warp_adjoint_tail(const f32x16 (&acc)[RT][PT], const NetDev& net, 
             }
         }
     }
+    if constexpr (UV_ONLY) return;
     if (geo.mode == 0) {
 #pragma unroll
         for (int e = 0; e < 9; ++e) {

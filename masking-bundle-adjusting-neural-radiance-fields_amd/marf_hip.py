@@ -75,6 +75,11 @@ _SIGS = {
                                         _c_vp, _c_vp, _c_vp, _c_vp]),
     "marf_warp_step_backward": (_c_int, [_c_vp, ctypes.POINTER(Geometry), _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_vp,
                                          _c_vp]),
+    "marf_gn_packed_bytes": (_c_sz, [_c_vp]),
+    "marf_gn_pack": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp]),
+    "marf_gn_scratch_bytes": (_c_sz, [_c_vp, ctypes.POINTER(Geometry)]),
+    "marf_gn_normal": (_c_int, [_c_vp, ctypes.POINTER(Geometry), ctypes.POINTER(C2f), _c_vp, _c_vp, _c_vp, _c_int,
+                                _c_vp, _c_vp, _c_vp, _c_vp]),
     "marf_net_layer_count": (_c_int, [_c_vp]),
     "marf_net_layer_span": (_c_int, [_c_vp, _c_int, ctypes.POINTER(_c_ll), ctypes.POINTER(_c_ll)]),
     "marf_comm_unique_id": (_c_int, [_c_vp, _c_sz]),
@@ -795,6 +800,90 @@ def render_warp_step(warp_weight, progress, engine, params, gt, mask, denom_over
                                          *[p.detach() for p in params])
 
 
+# ====================================================================== Gauss-Newton registration
+
+GN_VALS = 56  # per patch: sse, msum, g9 (9), the upper triangle of N (45)
+_GN_TRIU = None
+
+
+def gn_normal(warp_h, progress, engine, params, gt, mask, loss_only=False, want_rgb=True):
+    """marf_gn_normal on a frozen image: (out [B, 56] float64, rgb [B, Np, 3] or None).  Per patch
+    out = [sse, msum, g9 (9, over vec(H) row-major), N upper triangle row-major (45)]; loss_only runs
+    the forward alone and leaves only sse and msum defined (the full launch's bits).  warp_h: the
+    sl(3) parameters [B, 8].  The Gauss-Newton packed buffer is cached per parameter version."""
+    w = _f32(warp_h.detach(), "warp_param")
+    B = w.shape[0]
+    st = _stream(w)
+    Hm = torch.empty(B, 3, 3, device=w.device, dtype=torch.float32)
+    _check(lib().marf_sl3_to_SL3(_ptr(w), _ptr(Hm), B, engine.lie_batch(B), st))
+    geo = engine.grid_geo(B, Hm)
+    Np = geo_np(engine)
+    gt = _f32(gt, "labels").reshape(B, 3, Np)
+    mask = None if mask is None else _f32(mask.detach(), "masks").reshape(B, 1, Np)
+    packed = engine.gn_packed_for([p.detach() for p in params])
+    nbytes = lib().marf_gn_scratch_bytes(engine.net.handle, ctypes.byref(geo))
+    if nbytes == 0:
+        raise RuntimeError("libmarf: " + lib().marf_last_error().decode())
+    scratch = _BUFS.get("gn_scratch", nbytes, w.device)
+    rgb = torch.empty(B, Np, 3, device=w.device, dtype=torch.float32) if want_rgb else None
+    out = torch.zeros(B, GN_VALS, device=w.device, dtype=torch.float64)
+    cf = make_c2f(progress, engine.c2f)
+    _check(lib().marf_gn_normal(engine.net.handle, ctypes.byref(geo), ctypes.byref(cf), _ptr(packed), _ptr(gt), _ptr(mask),
+                                1 if loss_only else 0, _ptr(rgb), _ptr(out), _ptr(scratch), st))
+    return out, rgb
+
+
+def gn_tangent(h, lie_batch, se2=False):
+    """E_b = d vec(H_b) / d h_b [B, 9, 8] (float64) from one batched marf_sl3_to_SL3_backward call, 9
+    one-hot dH per patch; se2: followed by marf_se2_to_sl3_backward, [B, 9, 3]."""
+    h = _f32(h.detach(), "warp_param")
+    B = h.shape[0]
+    h9 = h[:, None, :].expand(B, 9, 8).reshape(B * 9, 8).contiguous()
+    dH = torch.eye(9, device=h.device, dtype=torch.float32)[None].expand(B, 9, 9).reshape(B * 9, 3, 3).contiguous()
+    dh = torch.empty(B * 9, 8, device=h.device, dtype=torch.float32)
+    st = _stream(h)
+    _check(lib().marf_sl3_to_SL3_backward(_ptr(h9), _ptr(dH), _ptr(dh), B * 9, lie_batch, st))
+    if se2:
+        dp = torch.empty(B * 9, 3, device=h.device, dtype=torch.float32)
+        _check(lib().marf_se2_to_sl3_backward(_ptr(dh), _ptr(dp), B * 9, st))
+        dh = dp
+    return dh.view(B, 9, -1).to(torch.float64)
+
+
+def gn_unpack(out):
+    """(sse [B], msum [B], g9 [B, 9], N [B, 9, 9] symmetric) of gn_normal's out."""
+    global _GN_TRIU
+    if _GN_TRIU is None:
+        _GN_TRIU = torch.triu_indices(9, 9)
+    iu = _GN_TRIU.to(out.device)
+    B = out.shape[0]
+    N = torch.zeros(B, 9, 9, device=out.device, dtype=out.dtype)
+    N[:, iu[0], iu[1]] = out[:, 11:56]
+    N[:, iu[1], iu[0]] = out[:, 11:56]
+    return out[:, 0], out[:, 1], out[:, 2:11], N
+
+
+def gn_system(out, E):
+    """The normal equations in the tangent: A = E^T N E [B, d, d], rhs = E^T g9 [B, d] (float64)."""
+    _, _, g9, N = gn_unpack(out)
+    Et = E.transpose(1, 2)
+    return Et @ N @ E, (Et @ g9[:, :, None])[:, :, 0]
+
+
+def gn_solve(A, rhs, lam, eps=1e-12):
+    """delta_b = -(A_b + lam_b diag(A_b) + eps I)^-1 rhs_b, batched in float64.  A patch whose system
+    cannot be solved (singular, or not finite) gets delta = 0, never a NaN; an all-zero system (msum =
+    0) solves to 0.  No host synchronisation: solve_ex reports instead of raising."""
+    d = A.shape[-1]
+    eye = torch.eye(d, device=A.device, dtype=A.dtype)
+    M = A + lam[:, None, None] * torch.diag_embed(torch.diagonal(A, dim1=1, dim2=2)) + eps * eye
+    M = torch.where(torch.isfinite(M).all(dim=(1, 2), keepdim=True), M, eye)
+    x, info = torch.linalg.solve_ex(M, rhs[:, :, None])
+    x = -x[:, :, 0]
+    ok = (info == 0) & torch.isfinite(x).all(dim=1) & torch.isfinite(rhs).all(dim=1)
+    return torch.where(ok[:, None], x, torch.zeros_like(x))
+
+
 def geo_np(engine):
     if not engine.crop:
         return engine.H * engine.W
@@ -841,6 +930,26 @@ class Engine:
         self.net.pack(flat, self._packed)
         self._packed_version = ver
         return self._packed
+
+    def gn_packed_for(self, params):
+        """packed_for of the Gauss-Newton path's own buffer (marf_gn_pack: the tile layouts, for a
+        bf16x3 net every image hi then lo), cached per parameter version the same way."""
+        ver = (PARAM_GENERATION[0],) + tuple((p.data_ptr(), p._version) for p in params)
+        if getattr(self, "_gn_packed", None) is not None and ver == self._gn_packed_version:
+            return self._gn_packed
+        dev = params[0].device
+        flat = flat_view(params)
+        if flat is None:
+            flat = torch.cat([p.detach().reshape(-1) for p in params])
+        _f32(flat, "mlp parameters")
+        nbytes = lib().marf_gn_packed_bytes(self.net.handle)
+        if nbytes == 0:
+            raise RuntimeError("libmarf: " + lib().marf_last_error().decode())
+        if getattr(self, "_gn_packed", None) is None or self._gn_packed.device != dev:
+            self._gn_packed = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        _check(lib().marf_gn_pack(self.net.handle, _ptr(flat), _ptr(self._gn_packed), _stream(flat)))
+        self._gn_packed_version = ver
+        return self._gn_packed
 
 
 # ====================================================================== implicit mask network

@@ -14,7 +14,9 @@ Same classes, attributes, state-dict keys and training-step order as the referen
 The arithmetic of the step runs in libmarf.so (marf_hip): Graph.forward is one fused HIP
 prologue+MLP kernel per tile, its backward the dgrad / warp-adjoint / weight-gradient kernels,
 the loss and Adam are HIP kernels too.  Patches shard over ranks (one process per GPU); the
-shared MLP gradient is summed with one RCCL all-reduce per step.
+shared MLP gradient is summed with one RCCL all-reduce per step.  On a frozen image (freeze_image) the
+warps move by Adam on the warp-only fused step or, with warp_solver: lm, by Levenberg-Marquardt on every
+patch's Gauss-Newton normal equations (Graph.lm_step over marf_gn_normal; an extension).
 """
 import json
 import os
@@ -168,6 +170,9 @@ class Model(torch.nn.Module):
                   dict(params=self.graph.warp_param.parameters(), lr=opt.optim.lr_warp)]
         if opt.get("freeze_image"):  # the image does not move: the warps (and the mask net, below) only
             groups = groups[1:]
+        if self.graph.warp_solver == "lm":  # the warps move by Graph.lm_step: no warp group, no optimizer
+            self.optim = None
+            return
         if opt.use_implicit_mask:
             # the shared mask network at its own rate (model/planar.py:95-96); embedding_view is in
             # no group, as in the reference: it keeps its random init
@@ -436,6 +441,10 @@ class Model(torch.nn.Module):
             var, loss = self.captured_step(var)
             if log_now:
                 self.summarize_loss({k: v for k, v in loss.items() if k != "all"})  # the NaN / Inf asserts
+        elif self.graph.warp_solver == "lm":  # Levenberg-Marquardt on the frozen image: no optimizer
+            var, loss = self.graph.lm_step(var)
+            # (the NaN / Inf asserts wait for the GPU: at logging steps only, as the captured step)
+            loss = self.summarize_loss(loss) if log_now else self._loss_sum(loss)
         else:
             self.optim.zero_grad()
             var = self.graph.forward(var, mode="train")
@@ -609,6 +618,28 @@ class Graph(torch.nn.Module):
                 raise NotImplementedError("freeze_image needs the fused step (fused_step: true): the separate "
                                           "forward / backward kernels differentiate the image")
             self.neural_image.requires_grad_(False)
+        # warp_solver: adam (the warp-only fused step and lr_warp) or lm (Levenberg-Marquardt on every
+        # patch's Gauss-Newton normal equations, marf_gn_normal; Model.lm_iteration)
+        self.warp_solver = str(opt.get("warp_solver") or "adam").lower()
+        if self.warp_solver not in ("adam", "lm"):
+            raise ValueError(f"warp_solver must be adam or lm, got {opt.get('warp_solver')}")
+        if self.warp_solver == "lm":
+            if not self.freeze_image:
+                raise NotImplementedError("warp_solver: lm needs freeze_image: the normal equations are those of "
+                                          "the warps on a frozen image (the image's parameters are not in them)")
+            if opt.use_implicit_mask:
+                raise NotImplementedError("warp_solver: lm with use_implicit_mask: a learned mask moves with the "
+                                          "warps and is not in the normal equations; use warp_solver: adam")
+            if _precision(opt) not in (marf_hip.MARF_FP32, marf_hip.MARF_BF16X3):
+                raise NotImplementedError(f"warp_solver: lm with precision {opt.get('precision')}: a 16-bit Jacobian "
+                                          "misses the warp gradient's bound; use fp32 or bf16x3")
+            if self.neural_image.skip:
+                raise NotImplementedError("warp_solver: lm with skip layers: the Gauss-Newton kernel takes no skip nets")
+            lm = opt.get("lm") or {}
+            self.lm = edict(lambda0=float(lm.get("lambda0", 1e-3)), up=float(lm.get("up", 10)),
+                            down=float(lm.get("down", 10)), lambda_min=float(lm.get("lambda_min", 1e-9)),
+                            lambda_max=float(lm.get("lambda_max", 1e9)))
+            self.lm_lambda = None  # [B] float64 on the device, created by the first iteration
 
     def warp_h(self):
         """The warps as the reference's sl(3) parameters [B, 8] (se2: the embedded generators)."""
@@ -700,6 +731,62 @@ class Graph(torch.nn.Module):
         else:
             var.edge_prediction = None
         return var
+
+    LM_EPS = 1e-12  # the eps I of the damped system: keeps an all-zero patch (msum = 0) solvable
+
+    @torch.no_grad()
+    def lm_step(self, var):
+        """One Levenberg-Marquardt iteration of every patch's registration on the frozen image
+        (warp_solver: lm), all launches with the band weights of the current progress:
+          a full marf_gn_normal launch at the accepted warps -> A = E^T N E, rhs = E^T g9 in the tangent
+          delta_b = -(A_b + lambda_b diag(A_b) + eps I)^-1 rhs_b   (batched float64 solve)
+          a loss-only launch at h + delta; per patch, sse_trial < sse takes the step and divides
+          lambda_b by `down`, otherwise h_b stays and lambda_b is multiplied by `up` (torch.where: no
+          host synchronisation).  fix_first keeps patch 0 where it is.
+        Fills var.rgb_prediction(_map) (the accepted warps' render) and returns the loss dict of
+        compute_loss: rgb = sum sse / (3 sum msum) at the accepted warps."""
+        opt = self.opt
+        imgs = var.images
+        w = self.warp_param.weight
+        B = w.shape[0]
+        se2 = opt.warp.type == "se2"
+        ni = self.neural_image
+        masks = imgs.masks if imgs.get("masks") is not None else None
+        if self.lm_lambda is None or self.lm_lambda.device != w.device:
+            self.lm_lambda = torch.full((B,), self.lm.lambda0, dtype=torch.float64, device=w.device)
+        h = self.warp_h().detach()
+        out, rgb = ni.render_gn(h, imgs.rgb, masks)
+        E = marf_hip.gn_tangent(h, ni.engine(w.device).lie_batch(B), se2=se2)
+        A, rhs = marf_hip.gn_system(out, E)
+        delta = marf_hip.gn_solve(A, rhs, self.lm_lambda, self.LM_EPS)
+        if opt.warp.fix_first:
+            delta[0] = 0
+        trial = (w.detach().to(torch.float64) + delta).to(torch.float32)
+        h_trial = marf_hip.se2_to_sl3(trial) if se2 else trial
+        out_t, _ = ni.render_gn(h_trial, imgs.rgb, masks, loss_only=True, want_rgb=False)
+        better = out_t[:, 0] < out[:, 0]
+        w.data.copy_(torch.where(better[:, None], trial, w.detach()))
+        lam = self.lm_lambda
+        self.lm_lambda = torch.where(better, (lam / self.lm.down).clamp_min(self.lm.lambda_min),
+                                     (lam * self.lm.up).clamp_max(self.lm.lambda_max))
+        self.lm_last = edict(sse=out[:, 0], sse_trial=out_t[:, 0], msum=out[:, 1], accepted=better, delta=delta)
+        var.fused_loss = None
+        var.rgb_prediction = rgb
+        var.rgb_prediction_map = rgb.view(B, int(self.h), int(self.w), 3).permute(0, 3, 1, 2)
+        var.edge_prediction = None
+        rgb_loss = (out[:, 0].sum() / (3 * out[:, 1].sum())).to(torch.float32)
+        loss = edict()
+        if opt.loss_weight.render is not None:
+            # compute_loss's terms: no learned mask; the edge term (logging only) is not evaluated here
+            edge_loss = torch.zeros((), dtype=torch.float64, device=w.device) if opt.use_edges else torch.tensor(0)
+            alpha = (opt.alpha_initial + (opt.alpha_final - opt.alpha_initial) * (self.it / self.max_iter)
+                     if opt.use_edges else 0)
+            loss.render = lin_comb([(1 - alpha, rgb_loss), (0.5, torch.tensor(0)), (alpha, edge_loss)])
+            loss.rgb = rgb_loss
+            loss.mask = torch.tensor(0)
+            loss.edge = edge_loss
+        self.it += 1
+        return var, loss
 
     def compute_loss(self, var, mode=None):
         loss = edict()
@@ -893,6 +980,15 @@ class NeuralImageFunction(torch.nn.Module):
         ps = self._params()
         return marf_hip.render_warp_step(warp_weight, self.progress.detach(), self.engine(warp_weight.device), ps, gt,
                                          masks, denom, b0, b1)
+
+    def render_gn(self, warp_weight, gt, masks, loss_only=False, want_rgb=True):
+        """The Gauss-Newton normal equations of every patch's registration on this (frozen) image at the
+        sl(3) warps warp_weight [B, 8]: (out [B, 56] float64, rgb [B, h*w, 3]) with out[b] = [sse, msum,
+        g9 (9), N upper triangle (45)] over vec(H_b) (marf_hip.gn_normal); loss_only: the forward, sse
+        and msum alone.  No autograd: the solver on top (Graph.lm_step) is explicit."""
+        ps = self._params()
+        return marf_hip.gn_normal(warp_weight, self.progress.detach(), self.engine(warp_weight.device), ps, gt, masks,
+                                  loss_only=loss_only, want_rgb=want_rgb)
 
     def forward(self, coord_2d):
         """rgb = MLP(cat[coord, posenc(coord)]) for explicit coordinates [..., 2] (:429-449)."""
