@@ -4,7 +4,13 @@ This is the only module that talks to the HIP library.  PyTorch is used for devi
 (caching allocator), the current HIP stream and autograd bookkeeping; every arithmetic step of
 the planar render loop runs in the library's kernels.  There is no CPU or eager-PyTorch fallback:
 if the library is missing or the tensors are not on a ROCm device the calls raise.
+
+Shared by the autograd functions: _planar_launch (the prologue of every planar launch), _step_forward
+(the full and the warp-only fused step), _scatter_rows, _soft_mask_grad and _Buffers.check (their
+backwards' tails), _PackedCache (packed weights per parameter version), flatten_params, _NativeNet (the
+handle of Net and MaskNet) and _nbytes (a size query whose 0 means refused).
 """
+import collections
 import ctypes
 import os
 
@@ -400,9 +406,48 @@ def posenc(coord, L, progress=None, c2f=None):
 
 # ====================================================================== MLP engine
 
-class Net:
+def _nbytes(fn, *args):
+    """A size query whose 0 means the library refused the request (the reason is marf_last_error)."""
+    n = fn(*args)
+    if n == 0:
+        raise RuntimeError("libmarf: " + lib().marf_last_error().decode())
+    return n
+
+
+class _NativeNet:
+    """A network plan behind one library handle.  A subclass names its entry points once
+    (DESTROY, PACK, SAVED_BYTES, WORKSPACE_BYTES) and sets self._h in its constructor."""
+
+    DESTROY = PACK = SAVED_BYTES = WORKSPACE_BYTES = None
+
+    @property
+    def handle(self):
+        return self._h
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None) and _lib is not None:
+                getattr(_lib, self.DESTROY)(self._h)
+        except Exception:
+            pass
+
+    def pack(self, flat_params, packed):
+        flat_params = _f32(flat_params, "mlp parameters")
+        _check(getattr(lib(), self.PACK)(self._h, _ptr(flat_params), _ptr(packed), _stream(flat_params)))
+
+    def saved_bytes(self, geo):
+        return getattr(lib(), self.SAVED_BYTES)(self._h, ctypes.byref(geo))
+
+    def workspace_bytes(self, geo):
+        return getattr(lib(), self.WORKSPACE_BYTES)(self._h, ctypes.byref(geo))
+
+
+class Net(_NativeNet):
     """An MLP shape + padding plan in the library (marf_net).  skip: the layer indices whose input
     is [previous output ; posenc features] (opt.arch.skip, model/planar.py:419-420, 440-441)."""
+
+    DESTROY, PACK = "marf_net_destroy", "marf_net_pack"
+    SAVED_BYTES, WORKSPACE_BYTES = "marf_saved_bytes", "marf_workspace_bytes"
 
     def __init__(self, dims, L, dtype, pixels_hint=0, skip=()):
         self.dims = [int(d) for d in dims]
@@ -427,38 +472,26 @@ class Net:
             _check(lib().marf_net_layer_span(h, l, ctypes.byref(off), ctypes.byref(n)))
             self.layer_spans.append((off.value, n.value))
 
-    @property
-    def handle(self):
-        return self._h
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) and _lib is not None:
-                _lib.marf_net_destroy(self._h)
-        except Exception:
-            pass
-
-    def pack(self, flat_params, packed):
-        _check(lib().marf_net_pack(self._h, _ptr(flat_params), _ptr(packed), _stream(flat_params)))
-
     def set_pipeline(self, mode=-1, wg_blocks=0, piece_tiles=0):
         """Pipelined weight gradients of the fused step (include/marf.h marf_net_set_pipeline):
         mode 0 off (default: measured slower), 1 on at any size, -1 large steps
         only.  Between steps only."""
         _check(lib().marf_net_set_pipeline(self._h, int(mode), int(wg_blocks), int(piece_tiles)))
 
-    def saved_bytes(self, geo):
-        return lib().marf_saved_bytes(self._h, ctypes.byref(geo))
-
-    def workspace_bytes(self, geo):
-        return lib().marf_workspace_bytes(self._h, ctypes.byref(geo))
+    def step_saved_bytes(self, geo):
+        return lib().marf_step_saved_bytes(self._h, ctypes.byref(geo))
 
     def warp_step_saved_bytes(self, geo):
         """marf_warp_step_saved_bytes; a net with no warp-only kernel raises with the library's reason."""
-        n = lib().marf_warp_step_saved_bytes(self._h, ctypes.byref(geo))
-        if n == 0:
-            raise RuntimeError("libmarf: " + lib().marf_last_error().decode())
-        return n
+        return _nbytes(lib().marf_warp_step_saved_bytes, self._h, ctypes.byref(geo))
+
+    def gn_packed_bytes(self):
+        """marf_gn_packed_bytes; a net the Gauss-Newton path refuses raises with the library's reason."""
+        return _nbytes(lib().marf_gn_packed_bytes, self._h)
+
+    def gn_pack(self, flat_params, packed):
+        flat_params = _f32(flat_params, "mlp parameters")
+        _check(lib().marf_gn_pack(self._h, _ptr(flat_params), _ptr(packed), _stream(flat_params)))
 
 
 def grid_geometry(B, H, W, patch_H, patch_W, Hm=None, crop=True):
@@ -496,8 +529,52 @@ class _Buffers:
     def generation(self, name, device):
         return self.gen.get((name, str(device)), 0)
 
+    def check(self, name, gen, device, what):
+        """Raise if the buffer was handed out again since generation `gen` (a backward whose saved
+        bytes a later forward overwrote); what: the subject of the message, e.g. "... buffers were"."""
+        if gen != self.generation(name, device):
+            raise RuntimeError(f"libmarf: {what} reused by a later forward; "
+                               "call backward() before the next Graph.forward")
+
 
 _BUFS = _Buffers()
+
+
+_Launch = collections.namedtuple("_Launch", "w h_local Hm geo Bl Np stream")
+
+
+def _planar_launch(warp_weight, engine, b0, b1):
+    """The prologue of a launch over patches [b0, b1) of warp_weight [B, 8]: the checked warps w, this
+    shard's rows h_local (the same storage when the shard is the whole batch), their matrices Hm
+    (marf_sl3_to_SL3, normalised over the full batch) and the pixel geometry on them."""
+    w = _f32(warp_weight, "warp_param")
+    Bl = b1 - b0
+    h_local = w[b0:b1].contiguous()
+    Hm = torch.empty(Bl, 3, 3, device=w.device, dtype=torch.float32)
+    st = _stream(w)
+    _check(lib().marf_sl3_to_SL3(_ptr(h_local), _ptr(Hm), Bl, engine.lie_batch(w.shape[0]), st))
+    return _Launch(w, h_local, Hm, engine.grid_geo(Bl, Hm), Bl, geo_np(engine), st)
+
+
+def _scatter_rows(dh_local, w, b0, b1):
+    """The gradient of rows [b0, b1) as a gradient of all of w: dh_local itself for the whole batch,
+    else zeros around it."""
+    if b1 - b0 == w.shape[0]:
+        return dh_local
+    dw = torch.zeros_like(w)
+    dw[b0:b1] = dh_local
+    return dw
+
+
+def _soft_mask_grad(ctx, rgb, stats, gout, stream):
+    """d (d_loss * loss) / d m of a learned (soft) mask from the step's own prediction and stats, in the
+    shape the mask came in; None for a fixed mask."""
+    if ctx.mask is None or not ctx.needs_input_grad[6]:
+        return None
+    d_mask = torch.empty_like(ctx.mask)
+    _check(lib().marf_masked_mse_mask_backward(_ptr(rgb), _ptr(ctx.gt), _ptr(ctx.mask), ctx.mask.shape[0],
+                                               ctx.mask.shape[2], _ptr(stats), _ptr(gout), _ptr(d_mask), stream))
+    return d_mask.view(ctx.mask_shape)
 
 
 def _split_grads(flat, shapes):
@@ -576,22 +653,16 @@ class _PlanarRenderFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, warp_weight, progress, engine, b0, b1, *params):
-        w = _f32(warp_weight, "warp_param")
-        Bl = b1 - b0
-        h_local = w[b0:b1].contiguous()
-        Hm = torch.empty(Bl, 3, 3, device=w.device, dtype=torch.float32)
-        st = _stream(w)
-        _check(lib().marf_sl3_to_SL3(_ptr(h_local), _ptr(Hm), Bl, engine.lie_batch(w.shape[0]), st))
-        geo = engine.grid_geo(Bl, Hm)
-        Np = geo_np(engine)
-        rgb = torch.empty(Bl, Np, 3, device=w.device, dtype=torch.float32)
+        ln = _planar_launch(warp_weight, engine, b0, b1)
+        w, geo = ln.w, ln.geo
+        rgb = torch.empty(ln.Bl, ln.Np, 3, device=w.device, dtype=torch.float32)
         packed = engine.packed_for(params)
         saved = _BUFS.get("planar_saved", engine.net.saved_bytes(geo), w.device)
         cf = make_c2f(progress, engine.c2f)
         _check(lib().marf_forward(engine.net.handle, ctypes.byref(geo), ctypes.byref(cf), _ptr(packed), _ptr(rgb),
-                                  _ptr(saved), st))
+                                  _ptr(saved), ln.stream))
         ctx.save_for_backward(w, progress, rgb)
-        ctx.Hm, ctx.h_local, ctx.saved_buf, ctx.packed, ctx.engine = Hm, h_local, saved, packed, engine
+        ctx.Hm, ctx.h_local, ctx.saved_buf, ctx.packed, ctx.engine = ln.Hm, ln.h_local, saved, packed, engine
         ctx.gen = _BUFS.generation("planar_saved", w.device)
         ctx.b0, ctx.b1 = b0, b1
         ctx.shapes = [p.shape for p in params]
@@ -601,9 +672,7 @@ class _PlanarRenderFunction(torch.autograd.Function):
     def backward(ctx, d_rgb):
         w, progress, rgb = ctx.saved_tensors
         engine = ctx.engine
-        if ctx.gen != _BUFS.generation("planar_saved", w.device):
-            raise RuntimeError("libmarf: the render's saved activations were reused by a later forward; "
-                               "call backward() before the next Graph.forward")
+        _BUFS.check("planar_saved", ctx.gen, w.device, "the render's saved activations were")
         Bl = ctx.b1 - ctx.b0
         geo = engine.grid_geo(Bl, ctx.Hm)
         d_rgb = _f32(d_rgb, "d_rgb")
@@ -615,13 +684,34 @@ class _PlanarRenderFunction(torch.autograd.Function):
         _check(lib().marf_backward(engine.net.handle, ctypes.byref(geo), ctypes.byref(cf), _ptr(ctx.packed),
                                    _ptr(ctx.h_local), engine.lie_batch(w.shape[0]), _ptr(rgb), _ptr(d_rgb),
                                    _ptr(ctx.saved_buf), _ptr(ws), _ptr(dflat), _ptr(dh_local), None, _stream(w)))
-        if Bl == w.shape[0]:
-            dw = dh_local
-        else:
-            dw = torch.zeros_like(w)
-            dw[ctx.b0:ctx.b1] = dh_local
-        grads = _split_grads(dflat, ctx.shapes)
-        return (dw, None, None, None, None, *grads)
+        dw = _scatter_rows(dh_local, w, ctx.b0, ctx.b1)
+        return (dw, None, None, None, None, *_split_grads(dflat, ctx.shapes))
+
+
+def _step_forward(ctx, buf, saved_bytes, entry, warp_weight, progress, engine, b0, b1, gt, mask, denom_override,
+                  params):
+    """The forward of both fused steps: launch `entry` (marf_step_forward or marf_warp_step_forward) with
+    the saved bytes in buffer `buf`, sized by saved_bytes(net, geo).  Leaves on ctx what both backwards
+    read and returns (w, rgb, stats) for the caller to save."""
+    ctx.set_materialize_grads(False)
+    ln = _planar_launch(warp_weight, engine, b0, b1)
+    w, geo, Bl, Np = ln.w, ln.geo, ln.Bl, ln.Np
+    gt = _f32(gt, "labels").reshape(Bl, 3, Np)
+    ctx.mask_shape = None if mask is None else mask.shape
+    mask = None if mask is None else _f32(mask, "masks").reshape(Bl, 1, Np)
+    rgb = torch.empty(Bl, Np, 3, device=w.device, dtype=torch.float32)
+    stats = torch.empty(3, device=w.device, dtype=torch.float32)
+    packed = engine.packed_for(params)
+    saved = _BUFS.get(buf, saved_bytes(engine.net, geo), w.device)
+    cf = make_c2f(progress, engine.c2f)
+    _check(entry(engine.net.handle, ctypes.byref(geo), ctypes.byref(cf), _ptr(packed), _ptr(gt), _ptr(mask),
+                 _ptr(denom_override), _ptr(rgb), _ptr(stats), _ptr(saved), ln.stream))
+    ctx.Hm, ctx.h_local, ctx.saved_buf, ctx.packed, ctx.engine = ln.Hm, ln.h_local, saved, packed, engine
+    ctx.gen = _BUFS.generation(buf, w.device)
+    ctx.gt, ctx.mask = gt, mask
+    ctx.b0, ctx.b1 = b0, b1
+    engine.last_stats = stats  # [loss, denominator, local 3*sum(mask)]
+    return w, rgb, stats
 
 
 class _PlanarStepFunction(torch.autograd.Function):
@@ -635,33 +725,11 @@ class _PlanarStepFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, warp_weight, progress, engine, b0, b1, gt, mask, denom_override, *params):
-        ctx.set_materialize_grads(False)
-        w = _f32(warp_weight, "warp_param")
-        Bl = b1 - b0
-        h_local = w[b0:b1].contiguous()
-        Hm = torch.empty(Bl, 3, 3, device=w.device, dtype=torch.float32)
-        st = _stream(w)
-        _check(lib().marf_sl3_to_SL3(_ptr(h_local), _ptr(Hm), Bl, engine.lie_batch(w.shape[0]), st))
-        geo = engine.grid_geo(Bl, Hm)
-        Np = geo_np(engine)
-        gt = _f32(gt, "labels").reshape(Bl, 3, Np)
-        ctx.mask_shape = None if mask is None else mask.shape
-        mask = None if mask is None else _f32(mask, "masks").reshape(Bl, 1, Np)
-        rgb = torch.empty(Bl, Np, 3, device=w.device, dtype=torch.float32)
-        stats = torch.empty(3, device=w.device, dtype=torch.float32)
-        packed = engine.packed_for(params)
-        saved = _BUFS.get("planar_step", lib().marf_step_saved_bytes(engine.net.handle, ctypes.byref(geo)), w.device)
-        cf = make_c2f(progress, engine.c2f)
-        _check(lib().marf_step_forward(engine.net.handle, ctypes.byref(geo), ctypes.byref(cf), _ptr(packed), _ptr(gt),
-                                       _ptr(mask), _ptr(denom_override), _ptr(rgb), _ptr(stats), _ptr(saved), st))
+        w, rgb, stats = _step_forward(ctx, "planar_step", Net.step_saved_bytes, lib().marf_step_forward, warp_weight,
+                                      progress, engine, b0, b1, gt, mask, denom_override, params)
         ctx.save_for_backward(w, progress, rgb, stats)
-        ctx.Hm, ctx.h_local, ctx.saved_buf, ctx.packed, ctx.engine = Hm, h_local, saved, packed, engine
-        ctx.gen = _BUFS.generation("planar_step", w.device)
-        ctx.gt, ctx.mask = gt, mask
-        ctx.b0, ctx.b1 = b0, b1
         ctx.params = params
         ctx.shapes = [p.shape for p in params]
-        engine.last_stats = stats  # [loss, denominator, local 3*sum(mask)]
         return rgb, stats[0]
 
     @staticmethod
@@ -671,9 +739,7 @@ class _PlanarStepFunction(torch.autograd.Function):
         n_in = 8 + len(ctx.shapes)
         if d_rgb is None and d_loss is None:
             return (None,) * n_in
-        if ctx.gen != _BUFS.generation("planar_step", w.device):
-            raise RuntimeError("libmarf: the fused step's saved buffers were reused by a later forward; "
-                               "call backward() before the next Graph.forward")
+        _BUFS.check("planar_step", ctx.gen, w.device, "the fused step's saved buffers were")
         Bl = ctx.b1 - ctx.b0
         geo = engine.grid_geo(Bl, ctx.Hm)
         alloc = torch.empty if d_loss is not None else torch.zeros  # the step backward writes every element
@@ -698,20 +764,9 @@ class _PlanarStepFunction(torch.autograd.Function):
             dh_local = dh_local + gs[0][ctx.b0:ctx.b1]
             dflat = dflat + torch.cat([g.reshape(-1) for g in gs[1:]])
         engine.last_flat_grad = dflat
-        if Bl == w.shape[0]:
-            dw = dh_local
-        else:
-            dw = torch.zeros_like(w)
-            dw[ctx.b0:ctx.b1] = dh_local
-        grads = _split_grads(dflat, ctx.shapes)
-        d_mask = None
-        if ctx.mask is not None and ctx.needs_input_grad[6] and d_loss is not None:
-            # a learned (soft) mask: d (d_loss * loss) / d m from the step's own prediction and stats
-            d_mask = torch.empty_like(ctx.mask)
-            _check(lib().marf_masked_mse_mask_backward(_ptr(rgb), _ptr(ctx.gt), _ptr(ctx.mask), Bl, ctx.mask.shape[2],
-                                                       _ptr(stats), _ptr(gout), _ptr(d_mask), _stream(w)))
-            d_mask = d_mask.view(ctx.mask_shape)
-        return (dw, None, None, None, None, None, d_mask, None, *grads)
+        dw = _scatter_rows(dh_local, w, ctx.b0, ctx.b1)
+        d_mask = _soft_mask_grad(ctx, rgb, stats, gout, _stream(w)) if d_loss is not None else None
+        return (dw, None, None, None, None, None, d_mask, None, *_split_grads(dflat, ctx.shapes))
 
 
 def render_step(warp_weight, progress, engine, params, gt, mask, denom_override=None, b0=0, b1=None):
@@ -727,33 +782,10 @@ class _PlanarWarpStepFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, warp_weight, progress, engine, b0, b1, gt, mask, denom_override, *params):
-        ctx.set_materialize_grads(False)
-        w = _f32(warp_weight, "warp_param")
-        Bl = b1 - b0
-        h_local = w[b0:b1].contiguous()
-        Hm = torch.empty(Bl, 3, 3, device=w.device, dtype=torch.float32)
-        st = _stream(w)
-        _check(lib().marf_sl3_to_SL3(_ptr(h_local), _ptr(Hm), Bl, engine.lie_batch(w.shape[0]), st))
-        geo = engine.grid_geo(Bl, Hm)
-        Np = geo_np(engine)
-        gt = _f32(gt, "labels").reshape(Bl, 3, Np)
-        ctx.mask_shape = None if mask is None else mask.shape
-        mask = None if mask is None else _f32(mask, "masks").reshape(Bl, 1, Np)
-        rgb = torch.empty(Bl, Np, 3, device=w.device, dtype=torch.float32)
-        stats = torch.empty(3, device=w.device, dtype=torch.float32)
-        packed = engine.packed_for(params)
-        saved = _BUFS.get("planar_warp_step", engine.net.warp_step_saved_bytes(geo), w.device)
-        cf = make_c2f(progress, engine.c2f)
-        _check(lib().marf_warp_step_forward(engine.net.handle, ctypes.byref(geo), ctypes.byref(cf), _ptr(packed),
-                                            _ptr(gt), _ptr(mask), _ptr(denom_override), _ptr(rgb), _ptr(stats),
-                                            _ptr(saved), st))
+        w, rgb, stats = _step_forward(ctx, "planar_warp_step", Net.warp_step_saved_bytes, lib().marf_warp_step_forward,
+                                      warp_weight, progress, engine, b0, b1, gt, mask, denom_override, params)
         ctx.save_for_backward(w, rgb, stats)
-        ctx.Hm, ctx.h_local, ctx.saved_buf, ctx.engine = Hm, h_local, saved, engine
-        ctx.gen = _BUFS.generation("planar_warp_step", w.device)
-        ctx.gt, ctx.mask = gt, mask
-        ctx.b0, ctx.b1 = b0, b1
         ctx.n_params = len(params)
-        engine.last_stats = stats  # [loss, denominator, local 3*sum(mask)]
         return rgb, stats[0]
 
     @staticmethod
@@ -767,9 +799,7 @@ class _PlanarWarpStepFunction(torch.autograd.Function):
                                "differentiate loss_rgb, or use render_step")
         if d_loss is None:
             return (None,) * n_in
-        if ctx.gen != _BUFS.generation("planar_warp_step", w.device):
-            raise RuntimeError("libmarf: the warp-only step's saved buffer was reused by a later forward; "
-                               "call backward() before the next Graph.forward")
+        _BUFS.check("planar_warp_step", ctx.gen, w.device, "the warp-only step's saved buffer was")
         Bl = ctx.b1 - ctx.b0
         geo = engine.grid_geo(Bl, ctx.Hm)
         dh_local = torch.empty(Bl, 8, device=w.device, dtype=torch.float32)
@@ -777,18 +807,8 @@ class _PlanarWarpStepFunction(torch.autograd.Function):
         _check(lib().marf_warp_step_backward(engine.net.handle, ctypes.byref(geo), _ptr(ctx.saved_buf), _ptr(ctx.h_local),
                                              engine.lie_batch(w.shape[0]), _ptr(gout), _ptr(stats), _ptr(dh_local),
                                              _stream(w)))
-        if Bl == w.shape[0]:
-            dw = dh_local
-        else:
-            dw = torch.zeros_like(w)
-            dw[ctx.b0:ctx.b1] = dh_local
-        d_mask = None
-        if ctx.mask is not None and ctx.needs_input_grad[6]:
-            # a learned (soft) mask: d (d_loss * loss) / d m from the step's own prediction and stats
-            d_mask = torch.empty_like(ctx.mask)
-            _check(lib().marf_masked_mse_mask_backward(_ptr(rgb), _ptr(ctx.gt), _ptr(ctx.mask), Bl, ctx.mask.shape[2],
-                                                       _ptr(stats), _ptr(gout), _ptr(d_mask), _stream(w)))
-            d_mask = d_mask.view(ctx.mask_shape)
+        dw = _scatter_rows(dh_local, w, ctx.b0, ctx.b1)
+        d_mask = _soft_mask_grad(ctx, rgb, stats, gout, _stream(w))
         return (dw, None, None, None, None, None, d_mask, None) + (None,) * ctx.n_params
 
 
@@ -811,25 +831,18 @@ def gn_normal(warp_h, progress, engine, params, gt, mask, loss_only=False, want_
     out = [sse, msum, g9 (9, over vec(H) row-major), N upper triangle row-major (45)]; loss_only runs
     the forward alone and leaves only sse and msum defined (the full launch's bits).  warp_h: the
     sl(3) parameters [B, 8].  The Gauss-Newton packed buffer is cached per parameter version."""
-    w = _f32(warp_h.detach(), "warp_param")
-    B = w.shape[0]
-    st = _stream(w)
-    Hm = torch.empty(B, 3, 3, device=w.device, dtype=torch.float32)
-    _check(lib().marf_sl3_to_SL3(_ptr(w), _ptr(Hm), B, engine.lie_batch(B), st))
-    geo = engine.grid_geo(B, Hm)
-    Np = geo_np(engine)
+    ln = _planar_launch(warp_h.detach(), engine, 0, warp_h.shape[0])  # (the whole batch: h_local is w, no copy)
+    w, geo, B, Np = ln.w, ln.geo, ln.Bl, ln.Np
     gt = _f32(gt, "labels").reshape(B, 3, Np)
     mask = None if mask is None else _f32(mask.detach(), "masks").reshape(B, 1, Np)
     packed = engine.gn_packed_for([p.detach() for p in params])
-    nbytes = lib().marf_gn_scratch_bytes(engine.net.handle, ctypes.byref(geo))
-    if nbytes == 0:
-        raise RuntimeError("libmarf: " + lib().marf_last_error().decode())
-    scratch = _BUFS.get("gn_scratch", nbytes, w.device)
+    scratch = _BUFS.get("gn_scratch", _nbytes(lib().marf_gn_scratch_bytes, engine.net.handle, ctypes.byref(geo)),
+                        w.device)
     rgb = torch.empty(B, Np, 3, device=w.device, dtype=torch.float32) if want_rgb else None
     out = torch.zeros(B, GN_VALS, device=w.device, dtype=torch.float64)
     cf = make_c2f(progress, engine.c2f)
     _check(lib().marf_gn_normal(engine.net.handle, ctypes.byref(geo), ctypes.byref(cf), _ptr(packed), _ptr(gt), _ptr(mask),
-                                1 if loss_only else 0, _ptr(rgb), _ptr(out), _ptr(scratch), st))
+                                1 if loss_only else 0, _ptr(rgb), _ptr(out), _ptr(scratch), ln.stream))
     return out, rgb
 
 
@@ -892,6 +905,36 @@ def geo_np(engine):
     return h * w
 
 
+class _PackedCache:
+    """One packed image of a net's fp32 master weights, packed again only when they changed: the key is
+    PARAM_GENERATION (in-library updates) plus every parameter's address and in-place version counter
+    (so every optimizer step triggers a re-pack).  nbytes() sizes the buffer, pack(flat, buf) fills it
+    and checks its input; the buffer follows the parameters to another device."""
+
+    def __init__(self, nbytes, pack):
+        self._nbytes, self._pack = nbytes, pack
+        self._buf = None
+        self._key = None
+
+    def invalidate(self):
+        self._key = None
+
+    def get(self, params):
+        key = (PARAM_GENERATION[0],) + tuple((p.data_ptr(), p._version) for p in params)
+        if self._buf is not None and key == self._key:
+            return self._buf
+        dev = params[0].device
+        flat = flat_view(params)
+        if flat is None:
+            flat = torch.cat([p.detach().reshape(-1) for p in params])
+        self._key = None  # (a pack that raises leaves nothing cached)
+        if self._buf is None or self._buf.device != dev:
+            self._buf = torch.empty(self._nbytes(), dtype=torch.uint8, device=dev)
+        self._pack(flat, self._buf)
+        self._key = key
+        return self._buf
+
+
 class Engine:
     """Library-side state of one NeuralImageFunction: net plan, packed weights, c2f, geometry."""
 
@@ -901,8 +944,9 @@ class Engine:
         self.H, self.W, self.patch_H, self.patch_W = H, W, patch_H, patch_W
         self.crop = bool(crop)
         self._lie_batch = lie_batch
-        self._packed = None
-        self._packed_version = None
+        net = self.net
+        self._packed = _PackedCache(lambda: net.packed_bytes, net.pack)
+        self._gn_packed = _PackedCache(net.gn_packed_bytes, net.gn_pack)  # (a refusing net raises at first use)
         self.last_flat_grad = None
         self.last_stats = None
         self.grad_events = None  # GradEvents: set by the Model for the bucketed gradient all-reduce
@@ -917,46 +961,27 @@ class Engine:
     def packed_for(self, params):
         """Pack the fp32 master weights into the MFMA operand layouts when they changed (tracked by
         the parameters' in-place version counters, so every optimizer step triggers a re-pack)."""
-        ver = (PARAM_GENERATION[0],) + tuple((p.data_ptr(), p._version) for p in params)
-        if self._packed is not None and ver == self._packed_version:
-            return self._packed
-        dev = params[0].device
-        flat = flat_view(params)
-        if flat is None:
-            flat = torch.cat([p.detach().reshape(-1) for p in params])
-        _f32(flat, "mlp parameters")
-        if self._packed is None or self._packed.device != dev:
-            self._packed = torch.empty(self.net.packed_bytes, dtype=torch.uint8, device=dev)
-        self.net.pack(flat, self._packed)
-        self._packed_version = ver
-        return self._packed
+        return self._packed.get(params)
 
     def gn_packed_for(self, params):
         """packed_for of the Gauss-Newton path's own buffer (marf_gn_pack: the tile layouts, for a
         bf16x3 net every image hi then lo), cached per parameter version the same way."""
-        ver = (PARAM_GENERATION[0],) + tuple((p.data_ptr(), p._version) for p in params)
-        if getattr(self, "_gn_packed", None) is not None and ver == self._gn_packed_version:
-            return self._gn_packed
-        dev = params[0].device
-        flat = flat_view(params)
-        if flat is None:
-            flat = torch.cat([p.detach().reshape(-1) for p in params])
-        _f32(flat, "mlp parameters")
-        nbytes = lib().marf_gn_packed_bytes(self.net.handle)
-        if nbytes == 0:
-            raise RuntimeError("libmarf: " + lib().marf_last_error().decode())
-        if getattr(self, "_gn_packed", None) is None or self._gn_packed.device != dev:
-            self._gn_packed = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        _check(lib().marf_gn_pack(self.net.handle, _ptr(flat), _ptr(self._gn_packed), _stream(flat)))
-        self._gn_packed_version = ver
-        return self._gn_packed
+        return self._gn_packed.get(params)
+
+    def invalidate_packed(self):
+        """Pack again at the next use whatever the versions say (a graph capture records the pack)."""
+        self._packed.invalidate()
+        self._gn_packed.invalidate()
 
 
 # ====================================================================== implicit mask network
 
-class MaskNet:
+class MaskNet(_NativeNet):
     """Shape + padding plan of the implicit-mask MLP in the library (marf_mask_net; reference
     model/planar.py:475-488 ImplicitMask with the :340-349 input).  Planning needs no GPU."""
+
+    DESTROY, PACK = "marf_mask_net_destroy", "marf_mask_net_pack"
+    SAVED_BYTES, WORKSPACE_BYTES = "marf_mask_saved_bytes", "marf_mask_workspace_bytes"
 
     def __init__(self, n_vocab, dtype, embed_dim=128, n_freqs=10, width=256, n_layers=5):
         h = _c_vp()
@@ -969,26 +994,6 @@ class MaskNet:
         self.param_count = lib().marf_mask_net_param_count(h)
         self.packed_bytes = lib().marf_mask_net_packed_bytes(h)
 
-    @property
-    def handle(self):
-        return self._h
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) and _lib is not None:
-                _lib.marf_mask_net_destroy(self._h)
-        except Exception:
-            pass
-
-    def pack(self, flat_params, packed):
-        _check(lib().marf_mask_net_pack(self._h, _ptr(flat_params), _ptr(packed), _stream(flat_params)))
-
-    def saved_bytes(self, geo):
-        return lib().marf_mask_saved_bytes(self._h, ctypes.byref(geo))
-
-    def workspace_bytes(self, geo):
-        return lib().marf_mask_workspace_bytes(self._h, ctypes.byref(geo))
-
 
 class MaskEngine:
     """Library-side state of one ImplicitMask: net plan, packed weights, pixel geometry."""
@@ -997,13 +1002,14 @@ class MaskEngine:
         self.net = MaskNet(n_vocab, dtype, **shape)
         self.H, self.W, self.patch_H, self.patch_W = H, W, patch_H, patch_W
         self.crop = bool(crop)
-        self._packed = None
-        self._packed_version = None
+        net = self.net
+        self._packed = _PackedCache(lambda: net.packed_bytes, net.pack)
 
     def geo(self, B):
         return grid_geometry(B, self.H, self.W, self.patch_H, self.patch_W, None, self.crop)
 
-    packed_for = Engine.packed_for
+    def packed_for(self, params):
+        return self._packed.get(params)
 
 
 class _MaskNetFunction(torch.autograd.Function):
@@ -1043,9 +1049,7 @@ class _MaskNetFunction(torch.autograd.Function):
     def backward(ctx, dm):
         (m,) = ctx.saved_tensors
         engine = ctx.engine
-        if ctx.gen != _BUFS.generation("mask_saved", m.device):
-            raise RuntimeError("libmarf: the mask net's saved activations were reused by a later forward; "
-                               "call backward() before the next Graph.forward")
+        _BUFS.check("mask_saved", ctx.gen, m.device, "the mask net's saved activations were")
         geo = engine.geo(ctx.B)
         dm = _f32(dm, "d_mask")
         ws = _BUFS.get("mask_ws", engine.net.workspace_bytes(geo), m.device)
@@ -1125,6 +1129,22 @@ def flat_view(tensors):
     return torch.empty(0, dtype=t0.dtype, device=t0.device).set_(st, off, (total,), (1,))
 
 
+def flatten_params(params):
+    """The parameters as a list, made consecutive views of one contiguous fp32 buffer when they are
+    not already (first use, a device move): the library reads them through that single pointer, one
+    pack and one Adam launch.  The Parameter objects stay (optimizer state, a captured graph); only
+    their .data is re-pointed."""
+    ps = list(params)
+    if flat_view(ps) is None:
+        flat = torch.cat([p.detach().reshape(-1) for p in ps]).contiguous()
+        off = 0
+        for p in ps:
+            n = p.numel()
+            p.data = flat[off:off + n].view_as(p)
+            off += n
+    return ps
+
+
 def render_train(warp_weight, progress, engine, params, b0=0, b1=None):
     b1 = warp_weight.shape[0] if b1 is None else b1
     if not torch.is_grad_enabled():
@@ -1135,17 +1155,11 @@ def render_train(warp_weight, progress, engine, params, b0=0, b1=None):
 def render_nograd(warp_weight, progress, engine, params, b0, b1):
     """Graph.forward without autograd (evaluation / render rate): the same fused grid -> warp ->
     posenc -> MLP kernel, nothing saved for a backward."""
-    w = _f32(warp_weight, "warp_param")
-    Bl = b1 - b0
-    h_local = w[b0:b1].contiguous()
-    Hm = torch.empty(Bl, 3, 3, device=w.device, dtype=torch.float32)
-    st = _stream(w)
-    _check(lib().marf_sl3_to_SL3(_ptr(h_local), _ptr(Hm), Bl, engine.lie_batch(w.shape[0]), st))
-    geo = engine.grid_geo(Bl, Hm)
-    rgb = torch.empty(Bl, geo_np(engine), 3, device=w.device, dtype=torch.float32)
+    ln = _planar_launch(warp_weight, engine, b0, b1)
+    rgb = torch.empty(ln.Bl, ln.Np, 3, device=ln.w.device, dtype=torch.float32)
     packed = engine.packed_for(params)
     cf = make_c2f(progress, engine.c2f)
-    _render(engine, geo, cf, packed, rgb, st)
+    _render(engine, ln.geo, cf, packed, rgb, ln.stream)
     return rgb
 
 

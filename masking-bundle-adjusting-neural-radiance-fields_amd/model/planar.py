@@ -322,7 +322,7 @@ class Model(torch.nn.Module):
                     self.optim._segments(group, advance=False)
             torch.cuda.current_stream(dev).wait_stream(side)
             self._drop_autograd(var)  # (no warm-up graph, whose gradient nodes live on `side`, stays alive)
-            self.graph.neural_image.engine(dev)._packed_version = None  # the repack must be recorded
+            self.graph.neural_image.engine(dev).invalidate_packed()  # the repack must be recorded
             steps = {st["step"] for st in self.optim.state.values() if "step" in st}
             if len(steps) > 1:
                 raise RuntimeError(f"captured_step: parameters at different Adam steps {sorted(steps)}")
@@ -670,15 +670,7 @@ class Graph(torch.nn.Module):
     def _mask_params(self):
         """The mask net's Linear parameters as consecutive views of one flat fp32 buffer (one pack,
         one Adam launch), re-flattened after a device move."""
-        ps = list(self.implicit_mask.parameters())
-        if marf_hip.flat_view(ps) is None:
-            flat = torch.cat([p.detach().reshape(-1) for p in ps]).contiguous()
-            off = 0
-            for p in ps:
-                n = p.numel()
-                p.data = flat[off:off + n].view_as(p)
-                off += n
-        return ps
+        return marf_hip.flatten_params(self.implicit_mask.parameters())
 
     def mask_engine(self, device):
         e = self._mask_engines.get(str(device))
@@ -936,15 +928,7 @@ class NeuralImageFunction(torch.nn.Module):
     def _params(self):
         """MLP parameters as consecutive views of one flat fp32 buffer (re-flattened after a
         device move); the library reads them through that single pointer."""
-        ps = list(self.mlp.parameters())
-        if marf_hip.flat_view(ps) is None:
-            flat = torch.cat([p.detach().reshape(-1) for p in ps]).contiguous()
-            off = 0
-            for p in ps:
-                n = p.numel()
-                p.data = flat[off:off + n].view_as(p)
-                off += n
-        return ps
+        return marf_hip.flatten_params(self.mlp.parameters())
 
     def engine(self, device):
         key = str(device)

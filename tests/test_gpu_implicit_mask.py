@@ -188,6 +188,23 @@ def test_step_gradient_into_a_soft_mask():
         assert e <= 1e-5, name
 
 
+def test_mask_net_stale_buffer_raises(tmp_path):
+    """The mask net's saved activations live in one buffer per device: a backward after a later forward
+    has reused it raises -- through the mask net alone, and through the whole training forward."""
+    from test_gpu_parity import small_setup
+    z, m, var, nl = small_setup("a", "fp32", tmp_path, use_implicit_mask=True)
+    m1 = m.graph.predict_mask(var.images.rgb)
+    assert m1.requires_grad
+    m.graph.predict_mask(var.images.rgb)  # reuses the saved activations
+    with pytest.raises(RuntimeError, match="mask net's saved activations were reused"):
+        m1.sum().backward()
+    v1 = m.graph.forward(var, mode="train")
+    l1 = m.graph.compute_loss(v1, mode="train").rgb
+    m.graph.forward(var, mode="train")
+    with pytest.raises(RuntimeError, match="reused"):
+        l1.backward()
+
+
 def _zero_edges(monkeypatch):
     """The fixtures' edge *prediction* is zero (ref_harness replaces the cv2 edge filter, which carries
     no gradient; the edge kernel has its own tests): the same stand-in here."""

@@ -124,7 +124,8 @@ def test_posenc_c2f(tag):
 SMALL = ("a", "b", "c", "d", "s1", "s2")  # s1, s2: arch.skip nets (tests/golden/step_skip.npz)
 
 
-def small_setup(tag, precision="fp32", tmp_path=None):
+def small_setup(tag, precision="fp32", tmp_path=None, **over):
+    """over: further model options; the fixture's state is then loaded into the keys it has."""
     from model import planar
     from util import EasyDict as edict
     z = g("step_skip" if tag.startswith("s") else "step_small")
@@ -134,13 +135,13 @@ def small_setup(tag, precision="fp32", tmp_path=None):
     opt = make_opt(tmp_path, H=int(H), W=int(W), patch_H=int(ph), patch_W=int(pw), batch_size=int(B),
                    max_iter=int(max_iter), use_edges=bool(use_edges), precision=precision,
                    arch={"layers": layers, "skip": skip, "posenc": ({"L_2D": int(L)} if L > 0 else None)},
-                   barf_c2f=None if c0 < 0 else [float(c0), float(c1)])
+                   barf_c2f=None if c0 < 0 else [float(c0), float(c1)], **over)
     m = planar.Model(opt)
     m.images = edict(rgb=t(z[f"{tag}_rgb"]), masks=t(z[f"{tag}_mask"]), masks_eroded=t(z[f"{tag}_mask"]),
                      edges=None, gt_hom=None, gt=None)
     m.build_networks()
     sd = {k[len(f"{tag}_init_"):]: torch.from_numpy(z[k]) for k in z.files if k.startswith(f"{tag}_init_")}
-    m.graph.load_state_dict(sd)
+    m.graph.load_state_dict(sd, strict=not over)
     m.graph.warp_param.weight.data.copy_(t(z[f"{tag}_warp0"]))
     if prog >= 0:
         m.graph.neural_image.progress.data.fill_(float(prog))
@@ -628,6 +629,17 @@ def test_fused_step_stale_buffer_raises(tmp_path):
     l1 = m.graph.compute_loss(v1, mode="train").rgb
     m.graph.forward(var, mode="train")  # reuses the saved buffers
     with pytest.raises(RuntimeError, match="reused"):
+        l1.backward()
+
+
+def test_render_stale_buffer_raises(tmp_path):
+    """The general render (fused_step off) keeps its activations in one buffer per device as well."""
+    z, m, var, nl = small_setup("a", "fp32", tmp_path, fused_step=False)
+    v1 = m.graph.forward(var, mode="train")
+    assert v1.fused_loss is None
+    l1 = m.graph.compute_loss(v1, mode="train").rgb
+    m.graph.forward(var, mode="train")  # reuses the saved activations
+    with pytest.raises(RuntimeError, match="render's saved activations were reused"):
         l1.backward()
 
 

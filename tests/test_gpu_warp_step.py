@@ -187,6 +187,19 @@ def test_soft_mask_gradient_is_render_steps(tmp_path):
         out_rgb.sum().backward()
 
 
+def test_warp_step_stale_buffer_raises(tmp_path):
+    """The warp-only step's dH partials live in one buffer per device: a backward after a later forward has
+    reused it raises, as the full step's does (test_gpu_parity.test_fused_step_stale_buffer_raises)."""
+    from test_gpu_parity import small_setup
+    z, m, var, nl = small_setup("a", "fp32", tmp_path, freeze_image=True)
+    v1 = m.graph.forward(var, mode="train")
+    assert v1.fused_loss is not None
+    l1 = m.graph.compute_loss(v1, mode="train").rgb
+    m.graph.forward(var, mode="train")  # reuses the saved buffer
+    with pytest.raises(RuntimeError, match="warp-only step's saved buffer was reused"):
+        l1.backward()
+
+
 def test_train_py_registers_on_a_loaded_image(tmp_path):
     """train.py --save_ckpt=true, then --load=... --freeze_image=true on the same patches: return code 0,
     finite losses, and the entire image renders bit-identically from both checkpoints."""
