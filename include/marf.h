@@ -263,6 +263,27 @@ int marf_gn_normal(const marf_net* net, const marf_geometry* geo, const marf_c2f
                    const float* d_gt, const float* d_mask, int loss_only, float* d_rgb, double* d_out, void* d_scratch,
                    void* stream);
 
+/* ---- Robust Gauss-Newton: iteratively reweighted least squares (IRLS) on the same problem, for a view
+ * with an occluder and no mask of it.  With r, J, m as above, e_q = sum_c r_qc^2, s_q = sqrt(e_q) and a
+ * scale delta > 0 in pixel-value units:
+ *     MARF_GN_HUBER :  rho(e) = e if e <= delta^2, else 2 delta s - delta^2;   w = 1, else delta / s
+ *     MARF_GN_CAUCHY:  rho(e) = delta^2 log1p(e / delta^2);                     w = 1 / (1 + e / delta^2)
+ * marf_gn_normal_robust writes d_out[b] = [cost = sum_q rho(e_q), msum = sum_q m_q (unweighted), g9 =
+ * sum_q w_q sum_c J_qc^T r_qc, N = sum_q w_q sum_c J_qc^T J_qc (upper triangle)]: the same 56 doubles, the
+ * same reduce, Triggs' first-order Hessian (no second-order term of rho), and d cost_b / d vec(H_b) = 2
+ * g9_b exactly.  d_weight [B][Np] fp32 (may be NULL) receives w_q of every real pixel, in the loss-only
+ * launch too: at the solution it is the view's inlier map.  d_rgb may be NULL.  The weight enters as
+ * sqrt(w) on the stored r and m of a slot, so w = 1 changes no bit: MARF_GN_HUBER with delta^2 at or above
+ * every e_q gives marf_gn_normal's 56 values and rgb bit for bit.  The packed buffer (marf_gn_pack) and the
+ * scratch (marf_gn_scratch_bytes) are marf_gn_normal's, as are its refusals and their reasons; in
+ * addition MARF_ERR_INVALID with the reason for an unknown kind and for a delta that is not finite or not
+ * > 0.  Two calls on the same inputs give the same bits; loss_only gives the full launch's cost bits. */
+#define MARF_GN_HUBER 1
+#define MARF_GN_CAUCHY 2
+int marf_gn_normal_robust(const marf_net* net, const marf_geometry* geo, const marf_c2f* c2f, const void* d_gn_packed,
+                          const float* d_gt, const float* d_mask, int loss_only, int kind, float delta, float* d_rgb,
+                          float* d_weight, double* d_out, void* d_scratch, void* stream);
+
 /* ---- MLP-gradient exchange of the patch-sharded step (the reference is
  * single-GPU, options.py:117-120, so this replaces no reference call: it is the one collective the
  * sharding adds).  RCCL over xGMI, librccl.so opened at first use.  marf_comm_unique_id fills 128

@@ -1897,18 +1897,23 @@ size_t marf_gn_scratch_bytes(const marf_net* net, const marf_geometry* geo) {
     return p.total;
 }
 
-int marf_gn_normal(const marf_net* net, const marf_geometry* geo, const marf_c2f* c2f, const void* d_gn_packed,
-                   const float* d_gt, const float* d_mask, int loss_only, float* d_rgb, double* d_out, void* d_scratch,
-                   void* stream) {
-    if (!net || !d_gn_packed || !d_gt || !d_out || !d_scratch) return fail(MARF_ERR_INVALID, "gn_normal: NULL argument");
+// marf_gn_normal (kind 0) and marf_gn_normal_robust (kind MARF_GN_HUBER / MARF_GN_CAUCHY): one plan, one
+// argument record, the tile kernel and the reduce
+static int gn_normal_launch(const char* who, const marf_net* net, const marf_geometry* geo, const marf_c2f* c2f,
+                            const void* d_gn_packed, const float* d_gt, const float* d_mask, int loss_only, int kind,
+                            float delta, float* d_rgb, float* d_weight, double* d_out, void* d_scratch, void* stream) {
+    if (!net || !d_gn_packed || !d_gt || !d_out || !d_scratch) return fail(MARF_ERR_INVALID, "%s: NULL argument", who);
     hipStream_t s = (hipStream_t)stream;
     GnNet q;
     GnPlan p;
     GnArgs ga;
     memset(&ga, 0, sizeof(ga));
     StepArgs& a = ga.s;
-    int rc = plan_gn_bufs(net, geo, "gn_normal", q, a.geo, p);
+    int rc = plan_gn_bufs(net, geo, who, q, a.geo, p);
     if (rc) return rc;
+    ga.robust_kind = kind;
+    ga.robust_delta = delta;
+    ga.weight = d_weight;
     fill_netdev(q.s, net->L, d_gn_packed, a.net);
     a.c2f = make_c2f(c2f);
     a.rgb = d_rgb;
@@ -1922,14 +1927,34 @@ int marf_gn_normal(const marf_net* net, const marf_geometry* geo, const marf_c2f
     ga.partial = (double*)(sv + p.part);
     if (net->L > 0) HIPCHK(marf_launch_c2f_weights(a.c2f, net->L, (float*)(sv + p.c2f), s), "gn_normal c2f");
     {
-        MarfProfScope ps(loss_only ? "gn_loss" : "gn", s);
-        HIPCHK(marf_launch_gn(ga, q.split, q.TP, loss_only != 0, q.lds, p.n_tiles, s), "gn_normal");
+        MarfProfScope ps(kind ? (loss_only ? "gn_robust_loss" : "gn_robust") : (loss_only ? "gn_loss" : "gn"), s);
+        HIPCHK(marf_launch_gn(ga, q.split, q.TP, loss_only != 0, q.lds, p.n_tiles, s, kind != 0), "gn_normal");
     }
     {
         MarfProfScope ps("gn_reduce", s);
         HIPCHK(marf_launch_gn_reduce(ga.partial, a.geo.Np_pad / q.TP, a.geo.B, loss_only != 0, d_out, s), "gn_normal reduce");
     }
     return MARF_OK;
+}
+
+int marf_gn_normal(const marf_net* net, const marf_geometry* geo, const marf_c2f* c2f, const void* d_gn_packed,
+                   const float* d_gt, const float* d_mask, int loss_only, float* d_rgb, double* d_out, void* d_scratch,
+                   void* stream) {
+    return gn_normal_launch("gn_normal", net, geo, c2f, d_gn_packed, d_gt, d_mask, loss_only, 0, 0.f, d_rgb, nullptr, d_out,
+                            d_scratch, stream);
+}
+
+static_assert(MARF_GN_HUBER == GN_HUBER && MARF_GN_CAUCHY == GN_CAUCHY, "marf.h and marf_args.h name the same losses");
+
+int marf_gn_normal_robust(const marf_net* net, const marf_geometry* geo, const marf_c2f* c2f, const void* d_gn_packed,
+                          const float* d_gt, const float* d_mask, int loss_only, int kind, float delta, float* d_rgb,
+                          float* d_weight, double* d_out, void* d_scratch, void* stream) {
+    if (kind != MARF_GN_HUBER && kind != MARF_GN_CAUCHY)
+        return fail(MARF_ERR_INVALID, "gn_normal_robust: unknown kind %d (MARF_GN_HUBER = 1, MARF_GN_CAUCHY = 2)", kind);
+    if (!std::isfinite(delta) || !(delta > 0.f))
+        return fail(MARF_ERR_INVALID, "gn_normal_robust: delta must be finite and > 0, got %g", (double)delta);
+    return gn_normal_launch("gn_normal_robust", net, geo, c2f, d_gn_packed, d_gt, d_mask, loss_only, kind, delta, d_rgb,
+                            d_weight, d_out, d_scratch, stream);
 }
 
 // ------------------------------------------------------------------ loss / optimizer

@@ -60,10 +60,16 @@ struct StepArgs {
 
 // Gauss-Newton normal equations on a frozen image (marf_gn.hip): the step's inputs (s: net, geo, c2f,
 // rgb, gt, mask, mask_bits, c2f_w, lda; nothing is saved, no dH / loss partials) and the per-tile
-// partials [n_tiles][56] = sse, msum, g9 (9), N upper triangle row-major (45).
+// partials [n_tiles][56] = sse, msum, g9 (9), N upper triangle row-major (45).  The robust
+// instantiations (marf_gn_normal_robust) read the last three: the loss (MARF_GN_HUBER / MARF_GN_CAUCHY),
+// its scale and the per-pixel weight map; the others never look at them.
+constexpr int GN_HUBER = 1, GN_CAUCHY = 2;  // include/marf.h's MARF_GN_HUBER / MARF_GN_CAUCHY
 struct GnArgs {
     StepArgs s;
     double* partial;
+    int robust_kind;
+    float robust_delta;
+    float* weight;  // out: [B][Np] IRLS weight of every real pixel (may be null)
 };
 
 // Implicit-mask network (marf_mask.hip; reference model/planar.py:340-349, 475-488): the per-pixel
@@ -377,10 +383,13 @@ hipError_t marf_launch_mlp_step(const marf::StepArgs& a, int dtype, int TP, int 
 hipError_t marf_launch_mlp_step_split(const marf::StepArgs& a, int TP, bool fwd_only, size_t lds, int n_tiles,
                                       hipStream_t s, bool warp_only = false);
 // the Gauss-Newton tile kernel (marf_gn.hip): split = the bf16x3 tile recipe (TP 128 or 64), else fp32
-// (TP 64); loss_only: forward, sse and msum only.  Then a patch's tile partials summed in tile order
-// into out [B][56] (loss_only: the first two values).
+// (TP 64); loss_only: forward, sse and msum only; robust: the IRLS instantiations (a.robust_kind,
+// a.robust_delta, a.weight).  Then a patch's tile partials summed in tile order into out [B][56]
+// (loss_only: the first two values).
 hipError_t marf_launch_gn(const marf::GnArgs& a, bool split, int TP, bool loss_only, size_t lds, int n_tiles,
-                          hipStream_t s);
+                          hipStream_t s, bool robust = false);
+hipError_t marf_launch_gn_robust(const marf::GnArgs& a, bool split, int TP, bool loss_only, size_t lds, int n_tiles,
+                                 hipStream_t s);  // (marf_gn_robust.hip; marf_launch_gn's robust branch)
 hipError_t marf_launch_gn_reduce(const double* partial, int tiles_per_patch, int B, bool loss_only, double* out,
                                  hipStream_t s);
 hipError_t marf_launch_c2f_weights(const marf::C2fDev& c, int L, float* out, hipStream_t s,

@@ -86,6 +86,8 @@ _SIGS = {
     "marf_gn_scratch_bytes": (_c_sz, [_c_vp, ctypes.POINTER(Geometry)]),
     "marf_gn_normal": (_c_int, [_c_vp, ctypes.POINTER(Geometry), ctypes.POINTER(C2f), _c_vp, _c_vp, _c_vp, _c_int,
                                 _c_vp, _c_vp, _c_vp, _c_vp]),
+    "marf_gn_normal_robust": (_c_int, [_c_vp, ctypes.POINTER(Geometry), ctypes.POINTER(C2f), _c_vp, _c_vp, _c_vp, _c_int,
+                                       _c_int, ctypes.c_float, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
     "marf_net_layer_count": (_c_int, [_c_vp]),
     "marf_net_layer_span": (_c_int, [_c_vp, _c_int, ctypes.POINTER(_c_ll), ctypes.POINTER(_c_ll)]),
     "marf_comm_unique_id": (_c_int, [_c_vp, _c_sz]),
@@ -823,6 +825,7 @@ def render_warp_step(warp_weight, progress, engine, params, gt, mask, denom_over
 # ====================================================================== Gauss-Newton registration
 
 GN_VALS = 56  # per patch: sse, msum, g9 (9), the upper triangle of N (45)
+GN_ROBUST = {"huber": 1, "cauchy": 2}  # marf.h's MARF_GN_HUBER / MARF_GN_CAUCHY by option name
 _GN_TRIU = None
 
 
@@ -831,6 +834,25 @@ def gn_normal(warp_h, progress, engine, params, gt, mask, loss_only=False, want_
     out = [sse, msum, g9 (9, over vec(H) row-major), N upper triangle row-major (45)]; loss_only runs
     the forward alone and leaves only sse and msum defined (the full launch's bits).  warp_h: the
     sl(3) parameters [B, 8].  The Gauss-Newton packed buffer is cached per parameter version."""
+    return _gn_launch(warp_h, progress, engine, params, gt, mask, loss_only, want_rgb, None)[:2]
+
+
+def gn_normal_robust(warp_h, progress, engine, params, gt, mask, kind, delta, loss_only=False, want_rgb=True,
+                     want_weight=True):
+    """marf_gn_normal_robust: gn_normal under a robust loss (kind: "huber" or "cauchy", or marf.h's
+    number; delta: its scale in pixel-value units): (out, rgb or None, weight [B, Np] float32 or None)
+    with out = [cost = sum rho, msum (unweighted), g9 and N weighted by the per-pixel IRLS weight],
+    which `weight` returns (written by the loss-only launch too).  An unknown kind, or a delta that
+    is not finite or not > 0, raises with the library's reason."""
+    kind = GN_ROBUST.get(kind, kind) if isinstance(kind, str) else kind
+    if not isinstance(kind, int):
+        raise ValueError(f"gn_normal_robust: kind must be one of {sorted(GN_ROBUST)}, got {kind!r}")
+    return _gn_launch(warp_h, progress, engine, params, gt, mask, loss_only, want_rgb, (kind, float(delta), want_weight))
+
+
+def _gn_launch(warp_h, progress, engine, params, gt, mask, loss_only, want_rgb, robust):
+    """The launch of gn_normal (robust None) and gn_normal_robust ((kind, delta, want_weight)):
+    (out, rgb, weight)."""
     ln = _planar_launch(warp_h.detach(), engine, 0, warp_h.shape[0])  # (the whole batch: h_local is w, no copy)
     w, geo, B, Np = ln.w, ln.geo, ln.Bl, ln.Np
     gt = _f32(gt, "labels").reshape(B, 3, Np)
@@ -841,9 +863,16 @@ def gn_normal(warp_h, progress, engine, params, gt, mask, loss_only=False, want_
     rgb = torch.empty(B, Np, 3, device=w.device, dtype=torch.float32) if want_rgb else None
     out = torch.zeros(B, GN_VALS, device=w.device, dtype=torch.float64)
     cf = make_c2f(progress, engine.c2f)
-    _check(lib().marf_gn_normal(engine.net.handle, ctypes.byref(geo), ctypes.byref(cf), _ptr(packed), _ptr(gt), _ptr(mask),
-                                1 if loss_only else 0, _ptr(rgb), _ptr(out), _ptr(scratch), ln.stream))
-    return out, rgb
+    if robust is None:
+        _check(lib().marf_gn_normal(engine.net.handle, ctypes.byref(geo), ctypes.byref(cf), _ptr(packed), _ptr(gt),
+                                    _ptr(mask), 1 if loss_only else 0, _ptr(rgb), _ptr(out), _ptr(scratch), ln.stream))
+        return out, rgb, None
+    kind, delta, want_weight = robust
+    weight = torch.empty(B, Np, device=w.device, dtype=torch.float32) if want_weight else None
+    _check(lib().marf_gn_normal_robust(engine.net.handle, ctypes.byref(geo), ctypes.byref(cf), _ptr(packed), _ptr(gt),
+                                       _ptr(mask), 1 if loss_only else 0, kind, delta, _ptr(rgb), _ptr(weight), _ptr(out),
+                                       _ptr(scratch), ln.stream))
+    return out, rgb, weight
 
 
 def gn_tangent(h, lie_batch, se2=False):

@@ -228,6 +228,10 @@ class Model(torch.nn.Module):
             self.metrics_file.close()
         if self.rank == 0 and self.opt.get("save_ckpt"):
             self.save_checkpoint(os.path.join(self.opt.output_path, "model.ckpt"))
+        if self.rank == 0 and self.graph.lm_robust is not None and getattr(self.graph, "lm_last", None) is not None:
+            # lm.robust: the per-pixel IRLS weight at the final warps -- the new views' inlier maps
+            wgt = self.graph.lm_last.weight.view(self.batch_size, int(self.graph.h), int(self.graph.w))
+            np.save(os.path.join(self.opt.output_path, "robust_weight.npy"), wgt.cpu().numpy().astype(np.float32))
         log.title("TRAINING DONE")
 
     # ------------------------------------------------------------------ checkpoints
@@ -623,6 +627,21 @@ class Graph(torch.nn.Module):
         self.warp_solver = str(opt.get("warp_solver") or "adam").lower()
         if self.warp_solver not in ("adam", "lm"):
             raise ValueError(f"warp_solver must be adam or lm, got {opt.get('warp_solver')}")
+        # lm.robust: none, or huber / cauchy -- IRLS on marf_gn_normal_robust with the scale lm.robust_delta
+        # (pixel-value units); self.lm_robust = (kind, delta), None for the plain least squares
+        lm = opt.get("lm") or {}
+        robust = str(lm.get("robust") or "none").lower()
+        if robust not in ("none",) + tuple(marf_hip.GN_ROBUST):
+            raise ValueError(f"lm.robust must be none, huber or cauchy, got {lm.get('robust')}")
+        self.lm_robust = None
+        if robust != "none":
+            if self.warp_solver != "lm":
+                raise ValueError(f"lm.robust: {robust} needs warp_solver: lm (the robust loss is the Levenberg-"
+                                 "Marquardt solver's; the Adam and fused steps have none)")
+            delta = float(lm.get("robust_delta", 0.1))
+            if not (np.isfinite(delta) and delta > 0):
+                raise ValueError(f"lm.robust_delta must be finite and > 0, got {lm.get('robust_delta')}")
+            self.lm_robust = (robust, delta)
         if self.warp_solver == "lm":
             if not self.freeze_image:
                 raise NotImplementedError("warp_solver: lm needs freeze_image: the normal equations are those of "
@@ -635,7 +654,6 @@ class Graph(torch.nn.Module):
                                           "misses the warp gradient's bound; use fp32 or bf16x3")
             if self.neural_image.skip:
                 raise NotImplementedError("warp_solver: lm with skip layers: the Gauss-Newton kernel takes no skip nets")
-            lm = opt.get("lm") or {}
             self.lm = edict(lambda0=float(lm.get("lambda0", 1e-3)), up=float(lm.get("up", 10)),
                             down=float(lm.get("down", 10)), lambda_min=float(lm.get("lambda_min", 1e-9)),
                             lambda_max=float(lm.get("lambda_max", 1e9)))
@@ -736,7 +754,12 @@ class Graph(torch.nn.Module):
           lambda_b by `down`, otherwise h_b stays and lambda_b is multiplied by `up` (torch.where: no
           host synchronisation).  fix_first keeps patch 0 where it is.
         Fills var.rgb_prediction(_map) (the accepted warps' render) and returns the loss dict of
-        compute_loss: rgb = sum sse / (3 sum msum) at the accepted warps."""
+        compute_loss: rgb = sum sse / (3 sum msum) at the accepted warps.
+        Under lm.robust (huber / cauchy) both launches are marf_gn_normal_robust's: A and rhs carry the
+        per-pixel IRLS weight, the accept test compares the robust costs, loss.rgb is sum cost / (3 sum
+        msum) -- the robust cost, not the mean squared error -- and the weights come back at the accepted
+        warps (the trial launch's where the step was taken, the full launch's where it was not):
+        lm_last.weight [B, h*w] and var.robust_weight_map [B, 1, h, w]."""
         opt = self.opt
         imgs = var.images
         w = self.warp_param.weight
@@ -747,7 +770,10 @@ class Graph(torch.nn.Module):
         if self.lm_lambda is None or self.lm_lambda.device != w.device:
             self.lm_lambda = torch.full((B,), self.lm.lambda0, dtype=torch.float64, device=w.device)
         h = self.warp_h().detach()
-        out, rgb = ni.render_gn(h, imgs.rgb, masks)
+        if self.lm_robust is None:
+            out, rgb = ni.render_gn(h, imgs.rgb, masks)
+        else:
+            out, rgb, wgt = ni.render_gn(h, imgs.rgb, masks, robust=self.lm_robust)
         E = marf_hip.gn_tangent(h, ni.engine(w.device).lie_batch(B), se2=se2)
         A, rhs = marf_hip.gn_system(out, E)
         delta = marf_hip.gn_solve(A, rhs, self.lm_lambda, self.LM_EPS)
@@ -755,13 +781,19 @@ class Graph(torch.nn.Module):
             delta[0] = 0
         trial = (w.detach().to(torch.float64) + delta).to(torch.float32)
         h_trial = marf_hip.se2_to_sl3(trial) if se2 else trial
-        out_t, _ = ni.render_gn(h_trial, imgs.rgb, masks, loss_only=True, want_rgb=False)
+        if self.lm_robust is None:
+            out_t, _ = ni.render_gn(h_trial, imgs.rgb, masks, loss_only=True, want_rgb=False)
+        else:
+            out_t, _, wgt_t = ni.render_gn(h_trial, imgs.rgb, masks, loss_only=True, want_rgb=False, robust=self.lm_robust)
         better = out_t[:, 0] < out[:, 0]
         w.data.copy_(torch.where(better[:, None], trial, w.detach()))
         lam = self.lm_lambda
         self.lm_lambda = torch.where(better, (lam / self.lm.down).clamp_min(self.lm.lambda_min),
                                      (lam * self.lm.up).clamp_max(self.lm.lambda_max))
         self.lm_last = edict(sse=out[:, 0], sse_trial=out_t[:, 0], msum=out[:, 1], accepted=better, delta=delta)
+        if self.lm_robust is not None:
+            self.lm_last.weight = torch.where(better[:, None], wgt_t, wgt)
+            var.robust_weight_map = self.lm_last.weight.view(B, 1, int(self.h), int(self.w))
         var.fused_loss = None
         var.rgb_prediction = rgb
         var.rgb_prediction_map = rgb.view(B, int(self.h), int(self.w), 3).permute(0, 3, 1, 2)
@@ -965,12 +997,17 @@ class NeuralImageFunction(torch.nn.Module):
         return marf_hip.render_warp_step(warp_weight, self.progress.detach(), self.engine(warp_weight.device), ps, gt,
                                          masks, denom, b0, b1)
 
-    def render_gn(self, warp_weight, gt, masks, loss_only=False, want_rgb=True):
+    def render_gn(self, warp_weight, gt, masks, loss_only=False, want_rgb=True, robust=None):
         """The Gauss-Newton normal equations of every patch's registration on this (frozen) image at the
         sl(3) warps warp_weight [B, 8]: (out [B, 56] float64, rgb [B, h*w, 3]) with out[b] = [sse, msum,
         g9 (9), N upper triangle (45)] over vec(H_b) (marf_hip.gn_normal); loss_only: the forward, sse
-        and msum alone.  No autograd: the solver on top (Graph.lm_step) is explicit."""
+        and msum alone.  No autograd: the solver on top (Graph.lm_step) is explicit.
+        robust = (kind, delta), kind "huber" or "cauchy": marf_hip.gn_normal_robust instead, (out, rgb,
+        weight [B, h*w]) with out[b] = [cost, msum, weighted g9 and N] and the per-pixel IRLS weight."""
         ps = self._params()
+        if robust is not None:
+            return marf_hip.gn_normal_robust(warp_weight, self.progress.detach(), self.engine(warp_weight.device), ps, gt,
+                                             masks, robust[0], robust[1], loss_only=loss_only, want_rgb=want_rgb)
         return marf_hip.gn_normal(warp_weight, self.progress.detach(), self.engine(warp_weight.device), ps, gt, masks,
                                   loss_only=loss_only, want_rgb=want_rgb)
 

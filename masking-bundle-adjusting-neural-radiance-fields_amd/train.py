@@ -2,6 +2,10 @@
 
     python train.py --group=<GROUP> --model=planar --yaml=planar --name=<NAME> --seed=3 --barf_c2f=[0,0.4]
 
+Register new views on a trained image (Levenberg-Marquardt; with --lm.robust=huber|cauchy the run ends by
+writing the per-pixel IRLS weights, float32 [B, h, w], to <output_path>/robust_weight.npy):
+    python train.py ... --load=<model.ckpt> --freeze_image=true --warp_solver=lm --lm.robust=cauchy --lm.robust_delta=0.01
+
 Multi-GPU (patches sharded over ranks, one process per GPU):
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 train.py ...
 """

@@ -2,7 +2,7 @@
 iteration (the warp-only fused step) of the same library on one GPU, and one end-to-end registration (no
 pass / fail: correctness is tested in tests/test_gpu_gn.py and tests/test_gpu_gn_solver.py).
 
-    python tools/bench_gn.py [--configs c1 c3] [--reps 20] [--warmup 5] [--e2e] [--out FILE]
+    python tools/bench_gn.py [--configs c1 c3] [--reps 20] [--warmup 5] [--robust huber cauchy] [--e2e] [--out FILE]
 
 Per config (c1, c3) and precision (fp32, bf16x3) two seeded frozen models on the same inputs -- `adam`
 (Model.train_iteration with freeze_image) and `lm` (the same with warp_solver: lm: one full and one
@@ -10,6 +10,9 @@ loss-only Gauss-Newton launch, the tangent chain and the batched solve) -- alter
 warm-up rounds, then `reps` rounds of one iteration each, timed with device events.  One JSON line per
 (config, precision): median, min and max per variant, then the per-launch HIP-event times
 (marf_profile_*: gn, gn_loss, gn_reduce beside mlp_step_warp, warp_bwd) of a few more iterations.
+--robust huber cauchy adds a model per loss (`lm_huber`, `lm_cauchy`: lm.robust at --robust-delta, the
+launches gn_robust and gn_robust_loss) to the same alternation, so the robust iteration stands beside the
+plain lm iteration of the same build, process and inputs.
 
 --e2e: the C1 problem (tests/golden/cat_batch3_c1.npz, seed 3, bf16x3) is trained for max_iter iterations
 and checkpointed; the same patches are then registered on the frozen image from the trained warps plus
@@ -67,9 +70,11 @@ def build(cfg, precision, solver, images, **over):
     return m, edict(idx=torch.arange(B), images=images)
 
 
-def bench(cfg, precision, reps, warmup):
+def bench(cfg, precision, reps, warmup, robust=(), delta=0.1):
     images = W.make_images(cfg)
     models = {s: build(cfg, precision, s, images) for s in ("adam", "lm")}
+    for kind in robust:
+        models["lm_" + kind] = build(cfg, precision, "lm", images, lm={"robust": kind, "robust_delta": delta})
 
     def it(name):
         def run():
@@ -142,6 +147,8 @@ def main():
     ap.add_argument("--precision", nargs="+", choices=PRECISIONS, default=PRECISIONS)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--robust", nargs="*", choices=["huber", "cauchy"], default=[])
+    ap.add_argument("--robust-delta", type=float, default=0.1)
     ap.add_argument("--e2e", action="store_true")
     ap.add_argument("--train-iters", type=int, default=3000)
     ap.add_argument("--adam-iters", type=int, default=3000)
@@ -161,7 +168,7 @@ def main():
 
     for cfg in a.configs:
         for prec in a.precision:
-            emit(bench(cfg, prec, a.reps, a.warmup))
+            emit(bench(cfg, prec, a.reps, a.warmup, a.robust, a.robust_delta))
             torch.cuda.empty_cache()
     if a.e2e:
         emit(e2e(a.train_iters, a.adam_iters, a.lm_iters, a.noise))
