@@ -1364,6 +1364,18 @@ def test_c5_shape_step_vs_oracle(precision, c2f, tmp_path):
         assert o["grad_err"] <= max(1e-5, 2 * o["grad_err_ref32"]), o
         assert o["dh_err"] <= max(1e-5, 2 * o["dh_err_ref32"]), o
     else:
+        # printed, not asserted: the plain-bf16 recipe's own error here (tests/plain16_ref.py, float64
+        # accumulation) and the kernel against that statement -- the warp-parity figure of the C5 line
+        import plain16_ref as P16
+        cfg, params, warp, rgb, mask, progress = inputs
+        t64 = P16.truth(inputs, torch.float64, DEV)
+        emu = P16.step(cfg, params, warp, rgb, mask, progress, T="bf16", device=DEV)
+        ours = {"grads": [(m.graph.neural_image.mlp[i].weight.grad.cpu().numpy(), m.graph.neural_image.mlp[i].bias.grad.cpu().numpy())
+                          for i in range(9)], "dh": m.graph.warp_param.weight.grad.cpu().numpy()}
+        e_emu, k_emu = P16.errs(emu, t64), P16.errs(ours, emu)
+        print("C5 bf16", "c2f" if c2f else "noc2f", "statement vs float64: grads %.2e dh %.2e | kernel vs float64: grads %.2e dh %.2e | "
+              "kernel vs statement (no pixel masked): grads %.2e dh %.2e" %
+              (max(e_emu[:-1]), e_emu[-1], o["grad_err"], o["dh_err"], max(k_emu[:-1]), k_emu[-1]))
         assert o["rgb"] <= 1e-2 and o["grad_cos"] >= 0.99 and o["dh_cos"] >= 0.98, o
 
 
