@@ -364,6 +364,45 @@ int marf_edge_map(const float* d_img, int n_img, int H, int W, double* d_out, vo
  * element, default anchor and border).  d_img [n_img][H][W] fp32 -> d_out (a different buffer). */
 int marf_erode_rect(const float* d_img, int n_img, int H, int W, int kh, int kw, float* d_out, void* stream);
 
+/* ---- Mosaic of the registered patches (an extension: the reference's only image is the neural image's own
+ * render, model/planar.py:211-217).  Every input patch is inverse-warped onto the canvas and blended; per
+ * canvas pixel the call reports the blended colour, the total weight, the number of contributing patches and
+ * the disagreement between them.
+ *
+ * Geometry is marf_pixel_grid's: canvas H x W; patch h x w = the crop window of (patch_H, patch_W) if crop
+ * (rows [y0, y0 + h) with y0 = H/2 - patch_H/2, h = (H/2 + patch_H/2) - y0 in integers, columns likewise: for even
+ * sizes h = patch_H, w = patch_W), else the canvas with y0 = x0 = 0; norm_w = W / max(H, W), norm_h = H / max(H, W);
+ * grid(k, n, norm) = ((k + 0.5) / n * 2 - 1) * norm.  For canvas pixel (i, j) and each patch b in index order:
+ *     y = (grid(j, W, norm_w), grid(i, H, norm_h));   (X0, X1, X2) = Hinv_b (y, 1);
+ *     (x, y~) = (X0, X1) / (X2 + 1e-8)                                      (marf_warp_points' arithmetic)
+ *     c = (x / norm_w + 1) W / 2 - 0.5 - x0,   r = (y~ / norm_h + 1) H / 2 - 0.5 - y0
+ * Patch b contributes iff X2 > 0 and -E <= c <= w - 1 + E and -E <= r <= h - 1 + E with E = 2^-10 px; c and r are
+ * then clamped to [0, w-1] and [0, h-1].  (E belongs to the definition: an identity warp puts the patch's border
+ * pixels on c = 0 exactly, and without E fp32 rounding would decide whether they are inside.)
+ *     v_b  = bilinear sample of d_img[b] (three channels) at (r, c)
+ *     m_b  = bilinear sample of d_weight[b] at (r, c); 1 if d_weight is NULL
+ *     f_b  = max(2^-10, (1 - |2c/(w-1) - 1|)(1 - |2r/(h-1) - 1|)) if feather, else 1
+ *     om_b = f_b m_b
+ * Outputs:  count = number of contributing patches with om_b > 0;  wsum = sum om_b;
+ *     image = sum om_b v_b / wsum (0 in all three channels where wsum == 0);
+ *     var   = sum om_b |v_b - image|^2 / (3 wsum): the mean over channels, >= 0, and 0 where count < 2.
+ * image and var accumulate in fp32 in patch order by a weighted Welford update (never as sum om v^2 / wsum -
+ * mean^2, which cancels); no atomics: two calls on the same inputs give the same bits.  d_weight = NULL gives
+ * the bits of an explicit map of ones; d_count / d_var = NULL change no bit of d_image and d_wsum.
+ * Hinv_b is the caller's: marf_sl3_to_SL3(-h_b), the exact inverse of expm(A(h_b)) (se2: of the embedded
+ * parameters).  Weights are expected >= 0: a contribution whose om_b is not > 0 (zero, negative, NaN) is left
+ * out of every output, wsum included.  MARF_ERR_INVALID with the reason, before any HIP call: a NULL d_Hinv /
+ * d_img / d_image / d_wsum, B < 1, non-positive sizes, a canvas side above 16384 (beyond it fp32 no longer holds
+ * the tolerance E beside w - 1), a patch larger than the canvas, feather with h < 2 or w < 2. */
+int marf_compose(int H, int W, int patch_H, int patch_W, int crop, int B,
+                 const float* d_Hinv   /* [B][9] row-major */,
+                 const float* d_img    /* [B][3][h*w]      */,
+                 const float* d_weight /* [B][1][h*w] or NULL = ones */,
+                 int feather,
+                 float* d_image /* [3][H*W] */, float* d_wsum /* [H*W] */,
+                 float* d_count /* [H*W] or NULL */, float* d_var /* [H*W] or NULL */,
+                 void* stream);
+
 /* ---- Adam (torch.optim.Adam, model/planar.py:98-99): one parameter segment, step >= 1.
  * d_grad_scale: optional device scalar multiplying the gradient (NULL = 1). */
 int marf_adam_step(float* d_p, const float* d_g, float* d_m, float* d_v, long long n, double lr, double beta1,

@@ -2189,6 +2189,48 @@ int marf_erode_rect(const float* d_img, int n_img, int H, int W, int kh, int kw,
 
 }  // extern "C"
 
+// ------------------------------------------------------------------ mosaic (marf_compose.hip)
+
+// (declared here, not in marf_args.h: the unit shares no new header with the others)
+hipError_t marf_launch_compose(int H, int W, int h, int w, int x0, int y0, float norm_h, float norm_w, int B,
+                               const float* Hinv, const float* img, const float* weight, int feather, float* image,
+                               float* wsum, float* count, float* var, hipStream_t s);
+
+extern "C" int marf_compose(int H, int W, int patch_H, int patch_W, int crop, int B, const float* d_Hinv,
+                            const float* d_img, const float* d_weight, int feather, float* d_image, float* d_wsum,
+                            float* d_count, float* d_var, void* stream) {
+    // every refusal before any HIP call
+    if (!d_Hinv || !d_img || !d_image || !d_wsum)
+        return fail(MARF_ERR_INVALID, "compose: d_Hinv, d_img, d_image and d_wsum must not be NULL");
+    if (B < 1) return fail(MARF_ERR_INVALID, "compose: B=%d, at least one patch is needed", B);
+    if (H <= 0 || W <= 0) return fail(MARF_ERR_INVALID, "compose: canvas %dx%d (sizes must be positive)", H, W);
+    // beside a coordinate of 16384 and more fp32 no longer holds the 2^-10 px validity tolerance
+    if (H > 16384 || W > 16384)
+        return fail(MARF_ERR_INVALID, "compose: canvas %dx%d, a side may be at most 16384 pixels", H, W);
+    int h = H, w = W, x0 = 0, y0 = 0;
+    if (crop) {
+        if (patch_H <= 0 || patch_W <= 0)
+            return fail(MARF_ERR_INVALID, "compose: patch %dx%d (sizes must be positive)", patch_H, patch_W);
+        if (patch_H > H || patch_W > W)
+            return fail(MARF_ERR_INVALID, "compose: patch %dx%d larger than the canvas %dx%d", patch_H, patch_W, H, W);
+        // marf_pixel_grid's integer crop window (warp.py:14-19)
+        y0 = H / 2 - patch_H / 2;
+        x0 = W / 2 - patch_W / 2;
+        h = (H / 2 + patch_H / 2) - y0;
+        w = (W / 2 + patch_W / 2) - x0;
+        if (h < 1 || w < 1) return fail(MARF_ERR_INVALID, "compose: patch %dx%d has an empty crop window", patch_H, patch_W);
+    }
+    if (feather && (h < 2 || w < 2))
+        return fail(MARF_ERR_INVALID, "compose: feather needs a patch of at least 2x2 (got %dx%d)", h, w);
+    const int mx = std::max(H, W);
+    MarfProfScope ps("compose", (hipStream_t)stream);
+    HIPCHK(marf_launch_compose(H, W, h, w, x0, y0, (float)((double)H / (double)mx), (float)((double)W / (double)mx), B,
+                               d_Hinv, d_img, d_weight, feather ? 1 : 0, d_image, d_wsum, d_count, d_var,
+                               (hipStream_t)stream),
+           "compose");
+    return MARF_OK;
+}
+
 // torch.optim.Adam's per-step scalars: bias corrections in python float64, step_size = lr / bc1,
 // bc2 ** 0.5, handed to the kernel as float
 static void adam_scalars(double lr, double beta1, double beta2, long long step, float& step_size, float& bc2_sqrt) {

@@ -98,6 +98,8 @@ _SIGS = {
     "marf_mse_workspace_bytes": (_c_sz, []),
     "marf_edge_map": (_c_int, [_c_vp, _c_int, _c_int, _c_int, _c_vp, _c_vp]),
     "marf_erode_rect": (_c_int, [_c_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_vp, _c_vp]),
+    "marf_compose": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp,
+                              _c_vp, _c_vp, _c_vp]),
     "marf_masked_mse": (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp]),
     "marf_masked_mse_backward": (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp]),
     "marf_masked_mse_mask_backward": (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp]),
@@ -1273,6 +1275,33 @@ def erode_rect(images, kernel=(5, 5)):
     out = torch.empty_like(x)
     _check(lib().marf_erode_rect(_ptr(x), B * C, H, W, int(kernel[1]), int(kernel[0]), _ptr(out), _stream(x)))
     return out
+
+
+# ====================================================================== mosaic
+
+def compose(H, W, ph, pw, crop, Hinv, img, weight=None, feather=False, want_var=True):
+    """The mosaic of B patches on the H x W canvas (marf_compose): Hinv [B, 3, 3] the inverse
+    homographies (sl3_to_SL3(-h)), img [B, 3, h, w], weight [B, 1, h, w] (any shape of B*h*w values) or None
+    for ones -> (image [3, H, W], wsum [1, H, W], count [1, H, W], var [1, H, W] or None).  Device tensors only."""
+    Hinv, img = _f32(Hinv, "Hinv"), _f32(img, "img")
+    weight = None if weight is None else _f32(weight, "weight")
+    B = Hinv.shape[0] if Hinv.dim() == 3 else Hinv.numel() // 9
+    if crop:
+        h = (H // 2 + ph // 2) - (H // 2 - ph // 2)
+        w = (W // 2 + pw // 2) - (W // 2 - pw // 2)
+    else:
+        h, w = H, W
+    if Hinv.numel() != B * 9 or img.numel() != B * 3 * h * w or (weight is not None and weight.numel() != B * h * w):
+        raise ValueError(f"compose: Hinv {tuple(Hinv.shape)}, img {tuple(img.shape)}, weight "
+                         f"{None if weight is None else tuple(weight.shape)} do not describe {B} patches of {h}x{w}")
+    dev = img.device
+    image = torch.empty(3, H, W, device=dev, dtype=torch.float32)
+    wsum = torch.empty(1, H, W, device=dev, dtype=torch.float32)
+    count = torch.empty(1, H, W, device=dev, dtype=torch.float32)
+    var = torch.empty(1, H, W, device=dev, dtype=torch.float32) if want_var else None
+    _check(lib().marf_compose(H, W, ph, pw, 1 if crop else 0, B, _ptr(Hinv), _ptr(img), _ptr(weight), 1 if feather else 0,
+                              _ptr(image), _ptr(wsum), _ptr(count), _ptr(var), _stream(img)))
+    return image, wsum, count, var
 
 
 # ====================================================================== Adam

@@ -137,7 +137,9 @@ class Model(torch.nn.Module):
             z = np.load(opt.dataset_npz, allow_pickle=False)
             rgb = torch.from_numpy(z["rgb"][:self.batch_size].astype(np.float32)).div(255)
             mask = torch.from_numpy(z["mask"][:self.batch_size].astype(np.float32))
-            self.images = edict(gt=None, rgb=rgb.to(opt.device), masks=mask.to(opt.device),
+            # optional: the ground-truth canvas (uint8 [3, H, W]) Model.evaluate scores the mosaic against
+            gt = torch.from_numpy(z["gt"].astype(np.float32)).div(255).to(opt.device) if "gt" in z.files else None
+            self.images = edict(gt=gt, rgb=rgb.to(opt.device), masks=mask.to(opt.device),
                                 masks_eroded=inputs.erode_images(mask, opt.device), gray=None, gt_hom=None)
             self.images.edges = None
             return
@@ -232,7 +234,78 @@ class Model(torch.nn.Module):
             # lm.robust: the per-pixel IRLS weight at the final warps -- the new views' inlier maps
             wgt = self.graph.lm_last.weight.view(self.batch_size, int(self.graph.h), int(self.graph.w))
             np.save(os.path.join(self.opt.output_path, "robust_weight.npy"), wgt.cpu().numpy().astype(np.float32))
+        if self.rank == 0 and self.graph.mosaic.eval:
+            self.write_mosaic()
         log.title("TRAINING DONE")
+
+    # ------------------------------------------------------------------ mosaic
+    @torch.no_grad()
+    def compose_mosaic(self, weights=None, feather=None):
+        """The input patches inverse-warped onto the canvas with the current warps and blended
+        (marf_compose): edict(image [3, H, W], wsum, count, var [1, H, W]).  weights (default:
+        mosaic.weights): mask = images.masks (ones if there are none), learned = the implicit mask network's
+        prediction, robust = the last lm.robust iteration's IRLS weights, ones.  feather: mosaic.feather."""
+        g, opt = self.graph, self.opt
+        weights = g.mosaic.weights if weights is None else str(weights).lower()
+        g.check_mosaic_weights(weights)
+        if self.world > 1:
+            raise ValueError("compose_mosaic with more than one process: the composition is single-process")
+        feather = g.mosaic.feather if feather is None else bool(feather)
+        rgb = self.images.rgb
+        if weights == "mask":
+            wgt = self.images.masks if self.images.get("masks") is not None else None
+        elif weights == "learned":
+            wgt = g.predict_mask(rgb).detach()  # [B, h*w, 1]: the [B][1][h*w] layout
+        elif weights == "robust":
+            if getattr(g, "lm_last", None) is None or g.lm_last.get("weight") is None:
+                raise RuntimeError("compose_mosaic(weights='robust'): no IRLS weights yet; run an lm iteration first")
+            wgt = g.lm_last.weight
+        else:
+            wgt = None
+        Hinv = marf_hip.sl3_to_SL3(-g.warp_h().detach())  # expm(-A(h)): the exact inverse of expm(A(h))
+        crop = bool(opt.use_cropped_images)
+        image, wsum, count, var = marf_hip.compose(int(opt.H), int(opt.W), int(g.h), int(g.w), crop, Hinv, rgb, wgt, feather)
+        return edict(image=image, wsum=wsum, count=count, var=var)
+
+    @torch.no_grad()
+    def evaluate(self, mosaic=None):
+        """What the registration gives (mosaic: a compose_mosaic result to score, default: a fresh one at the
+        option's weights), as a plain dict: coverage (share of canvas pixels with wsum > 0),
+        overlap (share with count >= 2), seam_rmse (sqrt of the mean of var over count >= 2: the RMS
+        disagreement of overlapping patches, NaN with no overlap; needs no ground truth) and, where
+        images.gt exists, psnr_mosaic_gt (over covered pixels; NaN, with a logged warning, if none is) and psnr_render_gt (predict_entire_image's
+        render over the whole canvas), both by the masked-MSE kernel with B = 1."""
+        opt = self.opt
+        mo = self.compose_mosaic() if mosaic is None else mosaic
+        covered, over = mo.wsum > 0, mo.count >= 2
+        res = dict(coverage=float(covered.to(torch.float64).mean()), overlap=float(over.to(torch.float64).mean()))
+        res["seam_rmse"] = float(mo.var[over].to(torch.float64).mean().sqrt()) if bool(over.any()) else float("nan")
+        gt = self.images.get("gt")
+        if gt is not None:
+            if tuple(gt.shape) != (3, int(opt.H), int(opt.W)):
+                raise ValueError(f"evaluate: images.gt is {tuple(gt.shape)}, the canvas [3, {opt.H}, {opt.W}]")
+            gtb = gt.to(device=mo.image.device, dtype=torch.float32).reshape(1, 3, -1)
+            pred = mo.image.reshape(3, -1).t().reshape(1, -1, 3).contiguous()
+            if bool(covered.any()):
+                mse = marf_hip.mse_stats(pred, gtb, covered.to(torch.float32).reshape(1, 1, -1))[0]
+                res["psnr_mosaic_gt"] = float(-10 * torch.log10(mse.to(torch.float64)))
+            else:  # nothing covered (every patch off the canvas, or all weights zero): no pixel to score
+                log.info("warning: evaluate: the mosaic covers no canvas pixel; psnr_mosaic_gt is NaN")
+                res["psnr_mosaic_gt"] = float("nan")
+            xy_grid = self.warp.get_normalized_pixel_grid()[:1]
+            render = self.graph.neural_image.forward(xy_grid).reshape(1, -1, 3)
+            res["psnr_render_gt"] = float(-10 * torch.log10(marf_hip.mse_stats(render, gtb)[0].to(torch.float64)))
+        return res
+
+    def write_mosaic(self):
+        """mosaic.eval: <output_path>/mosaic.npy (float32 [3, H, W]) and eval.json (Model.evaluate; a value
+        that is not finite -- seam_rmse without overlap -- is written as null)."""
+        mo = self.compose_mosaic()
+        np.save(os.path.join(self.opt.output_path, "mosaic.npy"), mo.image.cpu().numpy().astype(np.float32))
+        res = {k: (v if np.isfinite(v) else None) for k, v in self.evaluate(mo).items()}
+        with open(os.path.join(self.opt.output_path, "eval.json"), "w") as f:
+            json.dump(res, f, indent=1)
+        return res
 
     # ------------------------------------------------------------------ checkpoints
     def save_checkpoint(self, path):
@@ -658,6 +731,27 @@ class Graph(torch.nn.Module):
                             down=float(lm.get("down", 10)), lambda_min=float(lm.get("lambda_min", 1e-9)),
                             lambda_max=float(lm.get("lambda_max", 1e9)))
             self.lm_lambda = None  # [B] float64 on the device, created by the first iteration
+        # mosaic: the blend of Model.compose_mosaic / evaluate (marf_compose); eval: train.py writes
+        # mosaic.npy and eval.json when training ends
+        mo = opt.get("mosaic") or {}
+        self.mosaic = edict(eval=bool(mo.get("eval", False)), weights=str(mo.get("weights") or "mask").lower(),
+                            feather=bool(mo.get("feather", False)))
+        self.check_mosaic_weights(self.mosaic.weights)
+        if self.mosaic.eval and _dist() and torch.distributed.get_world_size() > 1:
+            raise ValueError("mosaic.eval with more than one process: the composition is single-process (every "
+                             "rank holds its own patches' warps only); run the evaluation in one process")
+
+    MOSAIC_WEIGHTS = ("mask", "learned", "robust", "ones")
+
+    def check_mosaic_weights(self, weights):
+        """Refuse (ValueError, with the reason) a mosaic blend weight this graph cannot supply."""
+        if weights not in self.MOSAIC_WEIGHTS:
+            raise ValueError(f"mosaic.weights must be one of {', '.join(self.MOSAIC_WEIGHTS)}, got {weights}")
+        if weights == "learned" and not self.opt.use_implicit_mask:
+            raise ValueError("mosaic.weights: learned needs use_implicit_mask (there is no mask network to ask)")
+        if weights == "robust" and self.lm_robust is None:
+            raise ValueError("mosaic.weights: robust needs lm.robust huber or cauchy (the weights are the IRLS "
+                             "solver's inlier map)")
 
     def warp_h(self):
         """The warps as the reference's sl(3) parameters [B, 8] (se2: the embedded generators)."""

@@ -6,6 +6,10 @@ Register new views on a trained image (Levenberg-Marquardt; with --lm.robust=hub
 writing the per-pixel IRLS weights, float32 [B, h, w], to <output_path>/robust_weight.npy):
     python train.py ... --load=<model.ckpt> --freeze_image=true --warp_solver=lm --lm.robust=cauchy --lm.robust_delta=0.01
 
+Write the mosaic of the input patches at the learned warps when training ends (<output_path>/mosaic.npy, float32
+[3, H, W], and eval.json: coverage, overlap, seam_rmse and, with a ground-truth image, two PSNRs; one process):
+    python train.py ... --mosaic.eval=true [--mosaic.weights=mask|learned|robust|ones] [--mosaic.feather=true]
+
 Multi-GPU (patches sharded over ranks, one process per GPU):
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 train.py ...
 """
